@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the low-bit FlashAttention-2 forward hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c4m|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c4m|c5] [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the whole operator (`lowbit_fa_qk_int8_pv_fp16_triton`: smooth-K mean + per-block
 quantisation of Q and K + fused attention) over one batch of synthetic fp16 inputs already resident in HBM.
@@ -11,7 +11,10 @@ that size (the op is independent per (batch, head): no data-path collective) - w
 Rank 0 prints ONE JSON line.  metric = attention TFLOP/s with the reference's FLOP formula
 4*B*H*D*S*S (halved for causal; utils/benchmark.py:212-214).
 
-Besides `value` (the default workload) the line carries, measured in the same process on the same device:
+A plain run sets up, warms up, times the K steps (`value`, `ms_per_step`, and `roofline` from HIP events around the attention
+launch of timed steps), writes the output of the last timed step if --dump-outputs is given, and prints the line.  Everything else
+runs only with --full: `accuracy` against fp32 SDPA, `fa2_reference` (torch's flash SDPA and this library's own fp16 kernel),
+`cpu_baseline`, and, measured in the same process on the same device:
   * `sweep` (N = 1): the whole BASELINE metric range - S in {4K, 8K, 16K, 32K} x D in {64, 128} x {non-causal, causal} for
     qk_int8_pv_fp16 plus C3 / C4 / C4-mixed / the C5 per-GPU shard - whole-operator and attention-kernel TFLOP/s, roofline
     fraction, torch's flash SDPA and this library's own fp16 kernel on the same inputs (example/draw/draw_single.py:15-21
@@ -52,6 +55,8 @@ WORKLOADS = {
 # reference's published TFLOP/s for the exact default workload (INT8 non-causal S=4K, B4 H32 D64,
 # hardware not stated, kernel-only timing): example/draw/draw_single.py:15-16
 PUBLISHED = {"c2": 199.5, "s8k": 201.59, "s16k": 200.47, "s32k": 201.16, "c2c": 167.77}
+# --dump-outputs: larger outputs are written as a sample of whole rows of this many bytes in fp32
+DUMP_MAX_BYTES = 32 << 20
 
 
 def log(*a):
@@ -124,6 +129,21 @@ def make_inputs(torch, dev, B, H, Hkv, S, D, layout, seed, dist_kind="normal", d
         k = torch.randint(-100, 100, shp_k, generator=g, device=dev).to(tdt)
     v = torch.randn(shp_k, generator=g, device=dev, dtype=torch.float32).to(tdt)
     return q, k, v
+
+
+def dump_outputs(torch, out_dir, o):
+    """--dump-outputs: what the timed path returned in its last step (the operator's `o`) as <out_dir>/o.npy in fp32.  An output
+    of more than DUMP_MAX_BYTES in fp32 is written as a fixed sample of its rows (one row = the head dim of one (batch, head,
+    token)): row indices drawn by numpy's default_rng(0), in ascending order, so the same arguments always pick the same rows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    out = o
+    rows = o.reshape(-1, o.shape[-1])
+    keep = DUMP_MAX_BYTES // (4 * rows.shape[1])
+    if rows.shape[0] > keep:
+        idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], keep, replace=False))
+        out = rows.index_select(0, torch.from_numpy(idx).to(rows.device))
+    np.save(os.path.join(out_dir, "o.npy"), out.float().cpu().numpy())
 
 
 def accuracy_vs_sdpa(torch, o, q, k, v, layout, causal, n_slices=4, row_chunk=2048):
@@ -331,6 +351,11 @@ def main():
                     help="un-counted operator launches for at least this long BEFORE the --warmup steps: the first launches "
                          "of a process run slow (clock ramp, code-object and allocator first touch), and 5 warm-up steps of "
                          "0.5 ms do not cover that")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: accuracy vs fp32 SDPA, torch's flash SDPA and "
+                         "the own fp16 kernel, the sweep, C5 strong scaling and the CPU baseline (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the output of the last timed step to DIR/o.npy (fp32; a fixed sample of rows beyond 32 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--kernel-timer-every", type=int, default=2,
                     help="bracket the attention kernel of every N-th timed step with HIP events (each pair costs the step ~6 us of "
@@ -340,6 +365,8 @@ def main():
     ap.add_argument("--no-sweep", action="store_true", help="skip the S x D x causal sweep (N = 1) that fills the `sweep` key")
     ap.add_argument("--no-c5", action="store_true", help="skip the C5 strong-scaling measurement that fills `c5_strong`")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import lowbit_quant_fa2_paddle_amd as lb
@@ -421,6 +448,8 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     flops_rank = 4.0 * B * H * D * S * S / (2 if causal else 1)
     value = world * flops_rank / (elapsed / args.steps) / 1e12
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, o)
 
     kern_all = sorted(ev[0].elapsed_time(ev[1]) for ev in attn_events)
     kern_ms = sum(kern_all) / max(len(kern_all), 1)
@@ -449,7 +478,7 @@ def main():
     # FA2-class fp16 comparison point on the SAME GPU and inputs (the reference's headline claim is "2.4x over
     # FlashAttention-2"): torch's flash-attention SDPA backend (AOTriton on ROCm).  Reported, never part of `value`.
     fa2 = None
-    if rank == 0 and not args.no_fa2 and api != "int8_fp8":
+    if args.full and rank == 0 and not args.no_fa2 and api != "int8_fp8":
         try:
             from torch.nn.attention import sdpa_kernel, SDPBackend
             qh, kh, vh = (t if layout == "HND" else t.transpose(1, 2) for t in (q, k, v))
@@ -483,22 +512,22 @@ def main():
                                   "lowbit_speedup_whole_op": round(dt / (elapsed / args.steps), 3)}
 
     acc = None
-    if rank == 0:
+    if args.full and rank == 0:
         acc = accuracy_vs_sdpa(torch, o, q, k, v, layout, causal)
     if distributed:
         dist.barrier()
     del q, k, v, o
     torch.cuda.empty_cache()
     sweep = None
-    if rank == 0 and world == 1 and not args.no_sweep and args.workload == "c2":
+    if args.full and rank == 0 and world == 1 and not args.no_sweep and args.workload == "c2":
         sweep = run_sweep(torch, lb, lib, dev)
     c5s = None
-    if not args.no_c5 and args.workload == "c2":
+    if args.full and not args.no_c5 and args.workload == "c2":
         c5s = c5_strong(torch, lb, dev, world, rank, distributed, dist if distributed else None, share)
     # the host-side baseline last: 12 s of all host cores and tens of GB of host memory in front of the big-footprint GPU runs above
     # coincided with `c5_strong` reading 25 % slow on some pool devices (round 4; the B = 4 shard of the same kernel was unaffected)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(B, H, S, D, causal)
 
     if rank == 0:
@@ -509,6 +538,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True,
             "scaling": "weak",
