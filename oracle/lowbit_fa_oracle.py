@@ -161,7 +161,7 @@ def per_block_int8(q, k, km, sm_scale, dtype: str, BLKQ=128, BLKK=64, q_qmax=127
 # --------------------------------------------------------------------------------------
 def attn_fwd_int8_fp16(q_i8, k_i8, v16, q_scale, k_scale, *, causal: bool, out_dtype: str = "fp16",
                        return_lse: bool = False, BLOCK_M: int = 128, BLOCK_N: int = 64,
-                       tail: str = "reference", pv_tile_fp16: bool = True):
+                       tail: str = "reference", pv_tile_fp16: bool = True, causal_mask: str = "reference"):
     """`_attn_fwd` + `_attn_fwd_inner` (src/triton/attn_qk_int8_per_block.py:69-167 / :24-66) and the
     causal pair (src/triton/attn_qk_int8_per_block_causal.py:82-214 / :24-79).
 
@@ -176,6 +176,9 @@ def attn_fwd_int8_fp16(q_i8, k_i8, v16, q_scale, k_scale, *, causal: bool, out_d
     `tail`: 'reference' = out-of-range K columns load as 0 so qk=0 takes part in the softmax
     (:48-49, the reference's ragged-tail defect); 'neg_inf' = masked with -inf (what
     the CUDA path does, csrc/qattn/attn_utils.cuh:327-353, and what the HIP kernel does).
+    `causal_mask`: 'reference' = the additive -1e6 of STAGE 2 (a key above the diagonal still takes part once scores reach
+    ~1e6 binades, q, k of ~1000 N(0,1)); 'neg_inf' = masked with -inf, as the HIP kernels and the CUDA path do.  The two agree
+    bit for bit while every score is far below 1e6 binades.
     Rows are independent, so the loop runs over key tiles with all participating rows at once.
     Returns (o [B,Hq,Sq,D] fp32-valued rounded to out_dtype, lse [B,Hq,Sq] fp32 or None).
     """
@@ -220,7 +223,10 @@ def attn_fwd_int8_fp16(q_i8, k_i8, v16, q_scale, k_scale, *, causal: bool, out_d
                     d1 = min(r0 + BLOCK_M, Sq)
                     rr = rows[r0:d1, None]
                     cc = (n0 + np.arange(BLOCK_N))[None, :]
-                    qk[: d1 - r0] = qk[: d1 - r0] + np.where(rr >= cc, np.float32(0), np.float32(-1000000.0))
+                    if causal_mask == "neg_inf":
+                        qk[: d1 - r0] = np.where(rr >= cc, qk[: d1 - r0], np.float32(-np.inf))
+                    else:
+                        qk[: d1 - r0] = qk[: d1 - r0] + np.where(rr >= cc, np.float32(0), np.float32(-1000000.0))
                 m_ij = np.maximum(m_i[r0:], qk.max(axis=1))
                 p = np.exp2(qk - m_ij[:, None]).astype(np.float32)
                 l_ij = p.sum(axis=1, dtype=np.float32)
@@ -261,14 +267,21 @@ def per_channel_fp8(v: np.ndarray):
 
 
 def attn_fwd_int8_fp8(q_i8, k_i8, v8, q_scale, k_scale, v_scale, *, causal: bool, out_dtype: str = "fp16",
-                      return_lse: bool = False, BLOCK_M: int = 128, BLOCK_N: int = 64):
+                      return_lse: bool = False, BLOCK_M: int = 128, BLOCK_N: int = 64, return_slack: bool = False,
+                      key_tiles_reversed: bool = False):
     """`qk_int_sv_f8_attn_kernel` semantics (csrc/qattn/qk_int_sv_f8_cuda.cu:46-692) on per-block
     scales: p = exp2(s - m + 8.807) so that p_max = 448 (csrc/qattn/attn_utils.cuh:30,424-445);
     l += sum(p) in fp32 before the fp8 rounding (:314-317); p -> e4m3 satfinite RN
     (attn_utils.cuh:470-485); PV e4m3 x e4m3 -> fp32 accumulate; O = (acc/l) * v_scale (:554-579);
     lse = log2(l) + m - 8.807 (:689).  Out-of-range keys are masked with -inf (attn_utils.cuh:327-353)
     and the causal mask is exact (-inf above the diagonal).
+    `return_slack`: also return `fp8_flip_slack(...)` (shaped like o, fp32, before the storage rounding); o and lse are
+    computed by the same code either way.
+    `key_tiles_reversed` (non-causal only): walk the 64-key tiles from the last to the first, as the HIP kernel does for every
+    other round of 64 Q blocks (L2 reuse).  P is rounded to e4m3 against the RUNNING row maximum, so the order changes which
+    references the codes are rounded against - by more than a rounding-boundary flip.
     """
+    assert not (causal and key_tiles_reversed)
     B, Hq, Sq, D = q_i8.shape
     _, Hkv, Sk, _ = k_i8.shape
     g = Hq // Hkv
@@ -290,7 +303,7 @@ def attn_fwd_int8_fp8(q_i8, k_i8, v8, q_scale, k_scale, v_scale, *, causal: bool
             m_i = np.full(Sq, -np.inf, np.float32)
             l_i = np.zeros(Sq, np.float32)
             acc = np.zeros((Sq, D), np.float32)
-            for j in range(n_kt):
+            for j in (range(n_kt - 1, -1, -1) if key_tiles_reversed else range(n_kt)):
                 n0 = j * BLOCK_N
                 n1 = min(n0 + BLOCK_N, Sk)
                 r0 = (n0 // BLOCK_M) * BLOCK_M if causal else 0
@@ -311,7 +324,188 @@ def attn_fwd_int8_fp8(q_i8, k_i8, v8, q_scale, k_scale, v_scale, *, causal: bool
             o[b, h] = acc / l_i[:, None] * v_scale[b, hk][None, :]
             if return_lse:
                 lse[b, h] = np.log2(l_i) + m_i - off
+    if return_slack:
+        slack = fp8_flip_slack(q_i8, k_i8, v8, q_scale, k_scale, v_scale, o, causal=causal, BLOCK_M=BLOCK_M, BLOCK_N=BLOCK_N,
+                               key_tiles_reversed=key_tiles_reversed)
+        return to_storage(o, out_dtype), lse, slack
     return to_storage(o, out_dtype), lse
+
+
+KMAGIC = 12582912.0  # 1.5 * 2^23: the bias a kernel may fold into its int32 scores (float(kMagic + s) == kMagic + s, |s| < 2^22)
+GRID_WIDE_LOG2G = -6  # a kernel that folds the bias keeps its per-tile scale on a grid of G / 2^22 only while log2(G) < -6
+
+
+def fp8_p_delta(S, M, A, sig, sig_m, same_tile, grid_g=None, s_int=None, t_int=None):
+    """Largest difference (binades) between the exponent argument of a CORRECT fp8-PV kernel and the exact one,
+    A = s sigma_j - t sigma_m + 8.807 (s, t integer scores, sigma = q_scale * k_scale as a real product; t, sigma_m those of the
+    running row maximum M = t sigma_m; S = s sigma_j).  Every term is a rounding of an fp32 operand the kernel has to form:
+
+      2^-22                       v_exp_f32: <= 1 ulp of P (2^-23 relative = 1.44 * 2^-23 binades)
+      2^-22 (|A| + 8.807)         the fma that forms the argument and the add of 8.807 to its constant: two roundings of at most
+                                  |A| + 8.807 each, 2^-24 per rounding, with a factor 2 so that +-2 ulps of the argument fit
+      2^-23 (|M| [|M| < 2^16] + sigma_j)
+                                  the row maximum rounded to fp32 (m_run) and the constant -m_run rounded again: 2 x 2^-24 |M|.
+                                  Beyond 2^16 binades a kernel must keep the reference as an exact product (m_run + m_lo, the
+                                  remainder form) - a reference rounded there moves P by percents - so the term drops out;
+                                  what is left is the rounding of r sigma - m_run (r the integer nearest to m / sigma: <= sigma).
+                                  (A reference taken while |M| < 2^16 and kept is covered by the first case.)
+      2^-24 |S - M|   (same tile) the dequantisation scale q_scale * k_scale rounded to fp32 once: when the score and the row
+      2^-24 (|S|+|M|) (otherwise) maximum come from the same key tile the SAME rounded scale multiplies both (the argument is
+                                  (s - t) * sc), otherwise each product carries its own rounding
+      grid (only while log2 G < -6, G = 2^(e + 1 - 21), 2^e <= 1.25 kMagic sigma_max < 2^(e+1), g = G 2^-22):
+        (|s| e_g(sigma_j) + |t| e_g(sigma_m))   a kernel that folds kMagic into its scores keeps the scale on multiples of g:
+                                  e_g(sigma) = g/2, or g - sigma where the grid rounds a tiny scale up to g
+        2^-23 kMagic (sigma_j + g)  its constant c1 = -kMagic sc - m + 8.807 is rounded twice at the size of kMagic * sc: two
+                                  half-ulps of that operand (one unit of the integer score times sigma, 1.5 sigma)
+
+    The grid terms are the only ones that do not scale with 2^-24 of |A|, |S| or |M|: at N(0,1) inputs they dominate
+    (sigma ~ 2^-12), and they are still a few ulps of the operand the kernel actually rounds, kMagic * sc.
+    """
+    S, M, A = np.abs(S), np.abs(M), np.abs(A)
+    d = 2.0 ** -22 + 2.0 ** -22 * (A + FP8_P_OFFSET) + 2.0 ** -23 * (np.where(M < 2.0 ** 16, M, 0.0) + sig)
+    d = d + 2.0 ** -24 * np.where(same_tile, np.abs(S - M), S + M)
+    if grid_g is not None:
+        g = grid_g
+
+        def e_g(sg):
+            return np.where(sg >= g / 2, g / 2, g - sg) + 2.0 ** -24 * sg
+        d = d + np.abs(s_int) * e_g(sig) + np.abs(t_int) * e_g(sig_m) + 2.0 ** -23 * KMAGIC * (sig + g)
+    return d
+
+
+def _grid_step(sc_max32: np.float32):
+    """g of a bias-folding kernel for the largest dequantisation scale of a (batch, kv-head, Q block), or None when the
+    kernel dequantises un-rounded from the start (log2 G >= -6)."""
+    x = np.float32(np.float32(1.25) * np.float32(np.float32(KMAGIC) * np.float32(sc_max32)))
+    e = int(np.frexp(np.float64(x))[1]) - 1  # 2^e <= x < 2^(e+1)
+    gexp = e + 1 - 21
+    if gexp >= GRID_WIDE_LOG2G:
+        return None
+    return 2.0 ** (gexp - 22)
+
+
+def fp8_flip_slack(q_i8, k_i8, v8, q_scale, k_scale, v_scale, o, *, causal: bool, BLOCK_M: int = 128, BLOCK_N: int = 64,
+                   key_tiles_reversed: bool = False):
+    """Per-element bound on |O_kernel - O_oracle| that comes from the e4m3 rounding of P (`attn_fwd_int8_fp8`, fp8-PV).
+
+    P = e4m3(exp2(A)) has 3 mantissa bits: an argument that differs by a few fp32 ulps moves P across a rounding boundary
+    of e4m3 and flips its code by one step (1/16 .. 1/8 of P).  The oracle's fp32 argument A32 and a correct kernel's
+    argument both lie near the EXACT argument A64 = s * (q_scale * k_scale) - M64 + 8.807, formed here in float64 from the
+    integer score and the exact running row maximum; the kernel within delta = fp8_p_delta(...) of it (derivation there).
+    So, per P:
+      * flip   = max(code(A+), code(A32)) - min(code(A-), code(A32)),  A+- = max/min(A64, A32) +- delta
+                 (every code the kernel may produce, and the oracle's code, lie in that range);
+      * rowsum = P64 (2^delta - 1) + |P64 - P32|: how far the fp32 row sum l (summed BEFORE the e4m3 rounding) may move.
+    Both are accumulated through the online-softmax rescales as acc and l are, and every rescale adds the error of its own
+    factor alpha (kernel: 2^-22 + the reference errors before and after; oracle: its exact deviation) times what had been
+    accumulated so far.  The result, in units of O:
+        slack = (flip_acc / l) * v_scale + |o| * rowsum_acc / l
+    i.e. the code flips moving the numerator, and a common factor 2^+-delta on P moving the row sum (this is what matters in
+    one-hot rows, where the largest P saturates at 448 while l keeps the exact sum).  Everything else - fp32 accumulation
+    order, one output ulp - is left to the checker's rtol / atol.  Returns fp32 [B, Hq, Sq, D].
+    """
+    B, Hq, Sq, D = q_i8.shape
+    _, Hkv, Sk, _ = k_i8.shape
+    g = Hq // Hkv
+    n_kt = (Sk + BLOCK_N - 1) // BLOCK_N
+    slack = np.zeros((B, Hq, Sq, D), np.float32)
+    rows = np.arange(Sq)
+    row_blk = rows // BLOCK_M
+    off = np.float32(FP8_P_OFFSET)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for b in range(B):
+            for h in range(Hq):
+                hk = h // g
+                qf = q_i8[b, h].astype(np.float32)
+                kf = k_i8[b, hk].astype(np.float32)
+                va = np.abs(v8[b, hk].astype(np.float64))
+                qs32 = q_scale[b, h][row_blk].astype(np.float32)
+                ks32 = k_scale[b, hk].astype(np.float32)
+                ks_max = np.float32(max(float(ks32.max()), 1e-30))
+                grid = np.array([_grid_step(np.float32(x * ks_max)) or 0.0 for x in q_scale[b, h].astype(np.float32)])[row_blk]
+                m32 = np.full(Sq, -np.inf, np.float32)          # the oracle's running max (fp32), as attn_fwd_int8_fp8
+                m64 = np.full(Sq, -np.inf)                      # exact running max
+                t_m = np.zeros(Sq)                              # its integer score, tile and scale
+                j_m = np.full(Sq, -1)
+                sig_m = np.zeros(Sq)
+                l32 = np.zeros(Sq, np.float32)
+                l64 = np.zeros(Sq)
+                fl_acc = np.zeros((Sq, D))                      # sum |code_hi - code_lo| |v8|
+                abs_acc = np.zeros((Sq, D))                     # sum code |v8|
+                rs = np.zeros(Sq)                               # row-sum slack
+                for j in (range(n_kt - 1, -1, -1) if key_tiles_reversed else range(n_kt)):
+                    n0 = j * BLOCK_N
+                    n1 = min(n0 + BLOCK_N, Sk)
+                    r0 = (n0 // BLOCK_M) * BLOCK_M if causal else 0
+                    if r0 >= Sq:
+                        break
+                    R = slice(r0, Sq)
+                    s_int = (qf[R] @ kf[n0:n1].T).astype(np.float64)
+                    sig = qs32[R].astype(np.float64) * float(ks32[j])
+                    qk32 = (qf[R] @ kf[n0:n1].T).astype(np.float32) * qs32[R, None] * ks32[j]
+                    S64 = s_int * sig[:, None]
+                    if causal:
+                        live = rows[R, None] >= (n0 + np.arange(n1 - n0))[None, :]
+                        qk32 = np.where(live, qk32, -np.inf)
+                        S64 = np.where(live, S64, -np.inf)
+                    # running maxima: the oracle's fp32 one and the exact one (with its integer score, tile and scale)
+                    mo32 = m32[R]
+                    mn32 = np.maximum(mo32, qk32.max(axis=1))
+                    arg = np.argmax(S64, axis=1)
+                    tmax = S64[np.arange(S64.shape[0]), arg]
+                    mo64 = m64[R]
+                    up = tmax > mo64
+                    mn64 = np.where(up, tmax, mo64)
+                    t_new = np.where(up, s_int[np.arange(S64.shape[0]), arg], t_m[R])
+                    sigm_new = np.where(up, sig, sig_m[R])
+                    jm_new = np.where(up, j, j_m[R])
+                    gr = grid[R]
+                    use_grid = gr > 0
+                    # rescale of what was accumulated: the oracle's alpha and a kernel's, against the exact factor
+                    prev = np.isfinite(mo64)
+                    a32 = np.where(prev, np.exp2(mo32 - mn32), 0.0).astype(np.float32)
+                    a64 = np.where(prev, np.exp2(mo64 - mn64), 0.0)
+                    # error of a rescale (only where the maximum moved): a kernel's factor carries the reference errors
+                    # before and after plus its exp2; the oracle's factor its own deviation from the exact one
+                    e_old = fp8_p_delta(mo64, mo64, 0.0, sig_m[R], sig_m[R], False, gr, t_m[R], t_m[R])
+                    e_new = fp8_p_delta(mn64, mn64, 0.0, sigm_new, sigm_new, False, gr, t_new, t_new)
+                    e_old = np.where(use_grid, e_old, fp8_p_delta(mo64, mo64, 0.0, sig_m[R], sig_m[R], False))
+                    e_new = np.where(use_grid, e_new, fp8_p_delta(mn64, mn64, 0.0, sigm_new, sigm_new, False))
+                    dev_o = np.abs(np.log2(np.where(a32 > 0, a32, 1.0)) - (mo64 - mn64))
+                    da = np.where(prev & up, 2.0 ** -22 + e_old + e_new + np.where(a32 > 0, dev_o, 0.0), 0.0)
+                    grow = np.exp2(np.minimum(da, 64.0)) - 1.0  # (capped: finite, and far beyond any P ratio that matters)
+                    fl_acc[R] = fl_acc[R] * a64[:, None] + np.where(abs_acc[R] > 0, grow[:, None] * abs_acc[R] * a64[:, None], 0.0)
+                    rs[R] = rs[R] * a64 + np.where(l64[R] > 0, grow * l64[R] * a64, 0.0)
+                    abs_acc[R] *= a64[:, None]
+                    l64[R] *= a64
+                    # P: the oracle's argument, the exact one, the window a kernel may use
+                    A32 = (qk32 - mn32[:, None] + off).astype(np.float32)
+                    A64 = S64 - mn64[:, None] + FP8_P_OFFSET
+                    same = (jm_new == j)[:, None]
+                    dk = fp8_p_delta(S64, mn64[:, None], A64, sig[:, None], sigm_new[:, None], same)
+                    dkg = fp8_p_delta(S64, mn64[:, None], A64, sig[:, None], sigm_new[:, None], same, gr[:, None],
+                                      s_int, t_new[:, None])
+                    dk = np.where(use_grid[:, None], dkg, dk)
+                    dead = ~np.isfinite(A64)
+                    lo = np.where(dead, -np.inf, np.minimum(A64, A32) - dk)
+                    hi = np.where(dead, -np.inf, np.maximum(A64, A32) + dk)
+                    c_o = np.where(dead, 0.0, e4m3fn_round(np.exp2(np.where(dead, -np.inf, A32)).astype(np.float32)))
+                    c_lo = e4m3fn_round(np.exp2(lo).astype(np.float32)).astype(np.float64)
+                    c_hi = e4m3fn_round(np.exp2(np.minimum(hi, 30.0)).astype(np.float32)).astype(np.float64)
+                    flip = np.maximum(c_hi, c_o) - np.minimum(c_lo, c_o)
+                    p64 = np.where(dead, 0.0, np.exp2(np.where(dead, -np.inf, A64)))
+                    p32 = np.exp2(np.where(dead, -np.inf, A32)).astype(np.float64)
+                    rsj = np.where(dead | (p64 + p32 == 0), 0.0, p64 * (np.exp2(np.minimum(dk, 64.0)) - 1.0) + np.abs(p64 - p32))
+                    fl_acc[R] += flip @ va[n0:n1]
+                    abs_acc[R] += np.maximum(c_hi, c_o) @ va[n0:n1]
+                    rs[R] += rsj.sum(axis=1)
+                    l64[R] += p64.sum(axis=1)
+                    l32[R] = l32[R] * a32 + p32.astype(np.float32).sum(axis=1, dtype=np.float32)
+                    m32[R], m64[R], t_m[R], j_m[R], sig_m[R] = mn32, mn64, t_new, jm_new, sigm_new
+                vs = v_scale[b, hk].astype(np.float64)[None, :]
+                l_lo = np.minimum(l64, l32.astype(np.float64))[:, None]
+                slack[b, h] = (fl_acc * vs + np.abs(o[b, h]).astype(np.float64) * rs[:, None]) / l_lo
+    return slack
 
 
 # --------------------------------------------------------------------------------------
@@ -346,7 +540,8 @@ def lowbit_fa_forward(q, k, v, *, dtype: str = "fp16", tensor_layout: str = "HND
                       sm_scale=None, smooth_k: bool = True, return_lse: bool = False,
                       q_qmax: float = 127.0, k_qmax: float = 127.0, pv: str = "fp16",
                       tail: str = "reference", amax_floor: float = 0.0, pv_tile_fp16: bool = True,
-                      return_intermediates: bool = False):
+                      return_intermediates: bool = False, return_slack: bool = False, causal_mask: str = "reference",
+                      fp8_key_tiles_reversed: bool = False):
     """`sageattn_qk_int8_pv_fp16_triton` (src/core.py:194-352); with q_qmax/k_qmax = 7 the intended
     semantics of `sageattn_qk_int4_pv_fp16_triton` (:945-1036, body defective - SURVEY 2.4-2/3); with
     pv='fp8' `sageattn_qk_int8_pv_fp8_cuda` (:735-941) on per-block scales.
@@ -355,7 +550,10 @@ def lowbit_fa_forward(q, k, v, *, dtype: str = "fp16", tensor_layout: str = "HND
     Steps: pad D (:277-287); km = mean_S(k) (:292-293); lse_correction = q.km (:294-304);
     bf16 -> v.half() (:307-308); sm_scale = D_og^-0.5 (:309-310); quant (:311-320); attention
     (:321-342); slice (:343); lse/1.44269504 + lse_correction*sm_scale (:344-350).
+    `return_slack` (pv='fp8' only): the e4m3 flip slack of O (`fp8_flip_slack`), laid out like o, is returned right after o.
     """
+    if return_slack and pv != "fp8":
+        raise ValueError("return_slack needs pv='fp8'")
     head_dim_og = q.shape[-1]
     q, k, v = _pad_head_dim(q), _pad_head_dim(k), _pad_head_dim(v)
     qc, kc, vc = _canon(q, tensor_layout), _canon(k, tensor_layout), _canon(v, tensor_layout)
@@ -375,24 +573,31 @@ def lowbit_fa_forward(q, k, v, *, dtype: str = "fp16", tensor_layout: str = "HND
                                                   amax_floor=amax_floor)
     if pv == "fp16":
         o, lse = attn_fwd_int8_fp16(q_i8, k_i8, v16, q_scale, k_scale, causal=is_causal, out_dtype=dtype,
-                                    return_lse=return_lse, tail=tail, pv_tile_fp16=pv_tile_fp16)
+                                    return_lse=return_lse, tail=tail, pv_tile_fp16=pv_tile_fp16, causal_mask=causal_mask)
         v_scale = None
     elif pv == "fp8":
         v8, v_scale = per_channel_fp8(vc)
-        o, lse = attn_fwd_int8_fp8(q_i8, k_i8, v8, q_scale, k_scale, v_scale, causal=is_causal, out_dtype=dtype,
-                                   return_lse=return_lse)
+        res = attn_fwd_int8_fp8(q_i8, k_i8, v8, q_scale, k_scale, v_scale, causal=is_causal, out_dtype=dtype,
+                                return_lse=return_lse, return_slack=return_slack, key_tiles_reversed=fp8_key_tiles_reversed)
+        o, lse = res[0], res[1]
+        slack = res[2] if return_slack else None
     else:
         raise ValueError(pv)
     o = o[..., :head_dim_og]
     if tensor_layout == "NHD":
         o = np.ascontiguousarray(np.transpose(o, (0, 2, 1, 3)))
+    if return_slack:
+        slack = slack[..., :head_dim_og]
+        if tensor_layout == "NHD":
+            slack = np.ascontiguousarray(np.transpose(slack, (0, 2, 1, 3)))
     if return_lse:
         lse = lse / np.float32(LOG2E)
         if smooth_k:
             lse = lse + lse_corr * np.float32(sm_scale)
+    head = (o, slack) if return_slack else (o,)
     if return_intermediates:
-        return o, lse, dict(q_i8=q_i8, q_scale=q_scale, k_i8=k_i8, k_scale=k_scale, km=km, v_scale=v_scale)
-    return (o, lse) if return_lse else o
+        return (*head, lse, dict(q_i8=q_i8, q_scale=q_scale, k_i8=k_i8, k_scale=k_scale, km=km, v_scale=v_scale))
+    return (*head, lse) if return_lse else (head if return_slack else o)
 
 
 # --------------------------------------------------------------------------------------

@@ -10,6 +10,8 @@ Bars:
   * LSE: <= 1e-3 abs;
   * sanity vs fp32 SDPA: MSE <= 1e-5 on N(0,1) inputs (int8), <= 1e-4 (fp8 PV, int4).
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -64,6 +66,41 @@ def _fp8_close(o, ref):
     err = np.abs(o - ref)
     bad = err > 1e-2 + 2e-2 * np.abs(ref)
     assert not bad.any(), f"max err {err.max():.3e} at {np.argwhere(bad)[:3].tolist()} ({bad.sum()} elements)"
+
+
+FP8_FLIP_RTOL = {"fp16": 2.0 ** -10 + 2.0 ** -12, "bf16": 2.0 ** -7 + 2.0 ** -12}
+FP8_FLIP_ATOL = 2.0 ** -12
+
+
+def _fp8_flip_close(o, ref, slack, dtype):
+    """fp8-PV against the oracle's restatement up to e4m3 rounding-boundary flips: per element
+        |o - ref| <= slack + rtol |ref| + atol
+    with `slack` from the oracle (`lowbit_fa_forward(..., pv="fp8", return_slack=True)`: the P codes a correct kernel may round
+    the other way, and the row-sum move that goes with them - see oracle.fp8_flip_slack).  What the slack leaves out:
+      * rtol: one output ulp - kernel and oracle each round their fp32 O to the storage dtype, so they may land one ulp apart,
+        <= 2^-10 |O| in fp16 and 2^-7 in bf16 - plus 2^-12 for the fp32 row sum l and the rescale factors alpha (summation order;
+        2^-24 per add, a few thousand adds at the longest sequences of the suite);
+      * atol = 2^-12: the difference of two fp32 accumulations of P V in different orders, about sqrt(n) 2^-24 sum|P V| / l,
+        sum|P V| / l <= max|v| <= 8 and n <= 2^15 keys: 2^-13.5 - plus fp16 subnormal spacing (2^-24).
+    Non-finite values must sit at the same positions with the same values.  Returns (worst |o - ref| / bound, share of
+    elements whose slack exceeds the rounding allowance rtol |ref| + atol, i.e. where the flips widen the bound at all)."""
+    o, ref, slack = (np.asarray(x, np.float64) for x in (o, ref, slack))
+    fin, fin_ref = np.isfinite(o), np.isfinite(ref)
+    assert np.array_equal(fin, fin_ref), f"non-finite at {np.argwhere(fin != fin_ref)[:3].tolist()} ({(fin != fin_ref).sum()} elements)"
+    assert np.array_equal(o[~fin], ref[~fin], equal_nan=True), "non-finite values differ"
+    o, ref, slack = o[fin], ref[fin], slack[fin]
+    assert np.isfinite(slack).all() and (slack >= 0).all(), "slack must be finite and non-negative"
+    err = np.abs(o - ref)
+    tol = slack + FP8_FLIP_RTOL[dtype] * np.abs(ref) + FP8_FLIP_ATOL
+    ratio = err / tol
+    bad = ratio > 1
+    worst = float(ratio.max()) if ratio.size else 0.0
+    frac = float((slack > FP8_FLIP_RTOL[dtype] * np.abs(ref) + FP8_FLIP_ATOL).mean()) if slack.size else 0.0
+    if os.environ.get("PYTEST_CURRENT_TEST"):
+        print(f"FP8BOUND {os.environ['PYTEST_CURRENT_TEST'].split(' ')[0]} worst={worst:.3f} slack_wide={frac:.4f}")
+    assert not bad.any(), (f"{bad.sum()} elements beyond slack + rtol|ref| + atol, worst ratio {worst:.2f}, "
+                           f"max err {err.max():.3e}")
+    return worst, frac
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -139,8 +176,9 @@ def test_attention_kernel_vs_reference_golden(oracle, dev, name):
     o, lse = attn.forward(q8, k8, tv, qs, ks, tensor_layout=p["layout"], output_dtype=TDT[p["dtype"]],
                           return_lse=True, is_causal=p["causal"])
     _golden_o_close(_np(o)[..., :p["D"]], g["o"], v, p)
-    # randint fixtures: |lse2| ~ 1e4, and the kernel's per-tile scale sits on a 2^-19-relative grid
-    assert np.abs(lse.cpu().numpy() - g["lse2"]).max() <= 1e-3 + 2.0 ** -18 * np.abs(g["lse2"]).max()
+    # randint fixtures: |lse2| ~ 1e4; off-grid blocks dequantise with the un-rounded scale since round 4 (worst case measured
+    # 2^-23.4 relative), so the relative term is a few fp32 roundings of the largest LSE
+    assert np.abs(lse.cpu().numpy() - g["lse2"]).max() <= 1e-3 + 2.0 ** -21 * np.abs(g["lse2"]).max()
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -228,9 +266,10 @@ def test_operator_int8_fp8_vs_oracle(oracle, dev, B, H, Hkv, S, D, layout, causa
     q, k, v = oracle.make_inputs(B, H, S, D, seed=31, layout=layout, dtype=dtype, Hkv=Hkv, k_bias=0.25)
     tq, tk, tv = (_t(a, dtype, dev) for a in (q, k, v))
     o, lse = lb.lowbit_fa_qk_int8_pv_fp8_cuda(tq, tk, tv, tensor_layout=layout, is_causal=causal, return_lse=True)
-    o_ref, lse_ref = oracle.lowbit_fa_forward(q, k, v, dtype=dtype, tensor_layout=layout, is_causal=causal,
-                                              return_lse=True, pv="fp8", amax_floor=1e-7)
+    o_ref, slack, lse_ref = oracle.lowbit_fa_forward(q, k, v, dtype=dtype, tensor_layout=layout, is_causal=causal,
+                                                     return_lse=True, pv="fp8", amax_floor=1e-7, return_slack=True)
     _fp8_close(_np(o), o_ref)
+    _fp8_flip_close(_np(o), o_ref, slack, dtype)
     assert np.abs(lse.cpu().numpy() - lse_ref).max() <= 2e-3 + 2.0 ** -9 * np.abs(lse_ref).max()
     ref = oracle.sdpa_naive(_canon(q, layout).astype(np.float64), _canon(k, layout).astype(np.float64),
                             _canon(v, layout).astype(np.float64), is_causal=causal)

@@ -40,7 +40,7 @@ def _o_close(o, ref, atol=2e-3, rtol=2e-3):
     assert not bad.any(), f"max err {err.max():.3e} at {np.argwhere(bad)[:3].tolist()} ({bad.sum()} elements)"
 
 
-from test_gpu_parity import _fp8_close  # noqa: E402
+from test_gpu_parity import _fp8_close, _fp8_flip_close  # noqa: E402
 
 
 @pytest.mark.parametrize("D", [64, 128])
@@ -96,11 +96,13 @@ def test_zero_k_block_in_a_masked_tile(oracle, dev, variant, S, causal, zero_lo,
         tol = dict(atol=2e-3, rtol=2e-3)
     else:
         o = lb.lowbit_fa_qk_int8_pv_fp8_cuda(tq, tk, tv, is_causal=causal, smooth_k=False)
-        ref = oracle.lowbit_fa_forward(q, k, v, is_causal=causal, smooth_k=False, pv="fp8", amax_floor=1e-7, tail="neg_inf")
+        ref, slack = oracle.lowbit_fa_forward(q, k, v, is_causal=causal, smooth_k=False, pv="fp8", amax_floor=1e-7, tail="neg_inf",
+                                              return_slack=True)
         tol = None  # fp8-PV: parity unpinned, loose against the oracle's restatement (_fp8_close)
     assert torch.isfinite(o).all()
     if tol is None:
         _fp8_close(_np(o), ref)
+        _fp8_flip_close(_np(o), ref, slack, "fp16")
     else:
         _o_close(_np(o), ref, **tol)
 
@@ -183,4 +185,10 @@ def test_reversed_rounds_of_q_blocks_vs_oracle(oracle, dev, D, S, first_rev_row,
         _o_close(_np(o)[:, :, rows], ref)
     else:
         _fp8_close(_np(o)[:, :, rows], ref)
+        # e4m3 P is rounded against the RUNNING row maximum, so the flip bound needs the kernel's tile order: the forward Q block
+        # (first 128 rows) walks the keys forwards, the blocks of the reversed round backwards
+        for r0, r1, rev in ((lo, lo + 128, False), (lo + 128, rows.stop, True)):
+            fr, sl = oracle.lowbit_fa_forward(q[:, :, r0:r1], k, v, amax_floor=1e-7, pv="fp8", return_slack=True,
+                                              fp8_key_tiles_reversed=rev)
+            _fp8_flip_close(_np(o)[:, :, r0:r1], fr, sl, "fp16")
     assert np.abs(lse.cpu().numpy()[:, :, rows] - lse_ref).max() <= (1e-3 if variant == "fp16" else 2e-3) + 2.0 ** -9 * np.abs(lse_ref).max()

@@ -244,13 +244,15 @@ def test_fp8_pv_on_the_bench_distribution(oracle, dev, D, causal):
     common factor per row: e4m3(P) / P of the dominant key) - it now dequantises them un-rounded (attn_fwd.hip, `wide`).
     fp8-PV parity itself stays unpinned: this is the HIP path against the oracle's restatement."""
     import lowbit_quant_fa2_paddle_amd as lb
-    from test_gpu_parity import _fp8_close
+    from test_gpu_parity import _fp8_close, _fp8_flip_close
     q, k, v = oracle.make_inputs(1, 2, 512, D, seed=5, dist="randint")
     tq, tk, tv = (_t(x, "fp16", dev) for x in (q, k, v))
     o, lse = _run_twice(lambda: lb.lowbit_fa_qk_int8_pv_fp8_cuda(tq, tk, tv, is_causal=causal, return_lse=True))
     assert torch.isfinite(o).all() and torch.isfinite(lse).all()
-    o_ref, lse_ref = oracle.lowbit_fa_forward(q, k, v, is_causal=causal, return_lse=True, pv="fp8", amax_floor=1e-7)
+    o_ref, slack, lse_ref = oracle.lowbit_fa_forward(q, k, v, is_causal=causal, return_lse=True, pv="fp8", amax_floor=1e-7,
+                                                     return_slack=True)
     _fp8_close(_np(o), o_ref)
+    _fp8_flip_close(_np(o), o_ref, slack, "fp16")
     assert np.abs(_np(lse) - lse_ref).max() <= 2e-3 + 2.0 ** -10 * np.abs(lse_ref).max()
 
 
@@ -260,7 +262,7 @@ def test_fp8_pv_largest_p_never_leaves_the_e4m3_range(oracle, dev):
     value that still rounds to 448; v_cvt_pk_fp8_f32 returns the NaN code beyond it, and the query's whole output row was NaN.
     Every output finite, and the head that failed against the oracle."""
     import lowbit_quant_fa2_paddle_amd as lb
-    from test_gpu_parity import _fp8_close
+    from test_gpu_parity import _fp8_close, _fp8_flip_close
     g = torch.Generator(device=dev)
     g.manual_seed(1234)
     B, H, S, D = 1, 8, 2048, 128
@@ -271,8 +273,9 @@ def test_fp8_pv_largest_p_never_leaves_the_e4m3_range(oracle, dev):
     assert torch.isfinite(o).all() and torch.isfinite(lse).all()
     h = 7
     qn, kn, vn = (x[:, h:h + 1].float().cpu().numpy() for x in (q, k, v))
-    o_ref = oracle.lowbit_fa_forward(qn, kn, vn, pv="fp8", amax_floor=1e-7)
+    o_ref, slack = oracle.lowbit_fa_forward(qn, kn, vn, pv="fp8", amax_floor=1e-7, return_slack=True)
     _fp8_close(_np(o[:, h:h + 1]), o_ref)
+    _fp8_flip_close(_np(o[:, h:h + 1]), o_ref, slack, "fp16")
 
 
 @pytest.mark.parametrize("op", ["int8", "fp8"])
@@ -290,7 +293,9 @@ def test_lse_overflows_exactly_where_the_reference_overflows(oracle, dev, op, D)
     fn = lb.lowbit_fa_qk_int8_pv_fp16_triton if op == "int8" else lb.lowbit_fa_qk_int8_pv_fp8_cuda
     o, lse = fn(tq, tk, tv, return_lse=True)
     with np.errstate(all="ignore"):
-        o_ref, lse_ref = oracle.lowbit_fa_forward(q, k, v, return_lse=True, amax_floor=1e-7, **({"pv": "fp8"} if op == "fp8" else {"tail": "neg_inf"}))
+        res = oracle.lowbit_fa_forward(q, k, v, return_lse=True, amax_floor=1e-7,
+                                       **({"pv": "fp8", "return_slack": True} if op == "fp8" else {"tail": "neg_inf"}))
+        o_ref, lse_ref = res[0], res[-1]
     assert torch.isfinite(o).all() and np.isfinite(o_ref).all()
     bad, bad_ref = ~np.isfinite(_np(lse)), ~np.isfinite(lse_ref)
     assert bad_ref.sum() > 100 and np.array_equal(bad, bad_ref)
@@ -298,8 +303,9 @@ def test_lse_overflows_exactly_where_the_reference_overflows(oracle, dev, op, D)
     if op == "int8":
         _o_close(_np(o), o_ref)
     else:  # (before the fp8 kernel re-referenced such scores - next test - 73 % of these rows missed the bound, by up to 11 x)
-        from test_gpu_parity import _fp8_close
+        from test_gpu_parity import _fp8_close, _fp8_flip_close
         _fp8_close(_np(o), o_ref)
+        _fp8_flip_close(_np(o), o_ref, res[1], "fp16")
 
 
 @pytest.mark.parametrize("dt,mul", [("fp16", 300.0), ("fp16", 1000.0), ("fp16", 1e4), ("bf16", 1e5), ("bf16", 1e7)])
@@ -311,17 +317,19 @@ def test_fp8_pv_on_scores_millions_of_binades_wide(oracle, dev, dt, mul, D, caus
     x1e5.  The fp8 kernel now keeps the reference as an exact product (m_run + m_lo) and takes the scores relative to it
     (attn_fwd.hip, `huge`): these rows are one-hot or nearly so and must match the oracle's restatement element for element."""
     import lowbit_quant_fa2_paddle_amd as lb
-    from test_gpu_parity import _fp8_close
+    from test_gpu_parity import _fp8_close, _fp8_flip_close
     rng = np.random.default_rng(int(mul) % 1000 + D)
     q, k, v = (rng.standard_normal((1, 2, 640, D)).astype(np.float32) for _ in range(3))
     q, k, v = oracle.to_storage(q * mul, dt), oracle.to_storage(k * mul, dt), oracle.to_storage(v, dt)
     tq, tk, tv = (_t(x, dt, dev) for x in (q, k, v))
     o, lse = _run_twice(lambda: lb.lowbit_fa_qk_int8_pv_fp8_cuda(tq, tk, tv, is_causal=causal, return_lse=True, smooth_k=False))
     with np.errstate(all="ignore"):
-        o_ref, lse_ref = oracle.lowbit_fa_forward(q, k, v, dtype=dt, is_causal=causal, return_lse=True, smooth_k=False, pv="fp8", amax_floor=1e-7)
+        o_ref, slack, lse_ref = oracle.lowbit_fa_forward(q, k, v, dtype=dt, is_causal=causal, return_lse=True, smooth_k=False, pv="fp8",
+                                                         amax_floor=1e-7, return_slack=True)
     assert np.isfinite(o_ref).all() and np.isfinite(lse_ref).all()
     assert torch.isfinite(o).all() and torch.isfinite(lse).all()
     _fp8_close(_np(o), o_ref)
+    _fp8_flip_close(_np(o), o_ref, slack, dt)
     assert np.abs(_np(lse) - lse_ref).max() <= 2.0 ** -20 * np.abs(lse_ref).max()
 
 
