@@ -157,11 +157,67 @@ def per_block_int8(q, k, km, sm_scale, dtype: str, BLKQ=128, BLKK=64, q_qmax=127
 
 
 # --------------------------------------------------------------------------------------
+# chosen Q blocks of a long sequence
+# --------------------------------------------------------------------------------------
+def block_rows(q_blocks, S: int, BLOCK_M: int = 128) -> np.ndarray:
+    """Absolute row indices of the Q blocks `q_blocks` (ascending block indices) of a sequence of S rows, in order: what a
+    caller slices out of Q (or of a device output) to hand the oracle's `q_blocks` paths."""
+    blocks = [int(b) for b in q_blocks]
+    assert blocks == sorted(set(blocks)) and blocks and 0 <= blocks[0] and blocks[-1] * BLOCK_M < S, (blocks, S)
+    return np.concatenate([np.arange(b * BLOCK_M, min((b + 1) * BLOCK_M, S)) for b in blocks])
+
+
+def _rows_of_blocks(q_blocks, n_rows: int, BLOCK_M: int = 128) -> np.ndarray:
+    """Absolute row indices of `n_rows` given rows that hold the Q blocks `q_blocks` back to back: whole blocks, only the last
+    one may be short (the ragged last block of the sequence).  None -> rows 0 .. n_rows - 1."""
+    if q_blocks is None:
+        return np.arange(n_rows)
+    blocks = [int(b) for b in q_blocks]
+    assert blocks == sorted(set(blocks)) and blocks and blocks[0] >= 0, blocks
+    last = n_rows - BLOCK_M * (len(blocks) - 1)
+    assert 0 < last <= BLOCK_M, f"{n_rows} rows cannot hold the blocks {blocks} (whole blocks, the last one may be short)"
+    return np.concatenate([np.arange(b * BLOCK_M, b * BLOCK_M + (BLOCK_M if i + 1 < len(blocks) else last))
+                           for i, b in enumerate(blocks)])
+
+
+def _split_by_direction(q_blocks, n_blocks: int, key_tiles_reversed):
+    """Per-block key-tile order: `key_tiles_reversed` is one bool for the call or one per given Q block.  -> None when every
+    block walks the same way, else the two lists of given-block positions (forward, reversed)."""
+    if isinstance(key_tiles_reversed, (bool, np.bool_)):
+        return None
+    rev = [bool(r) for r in key_tiles_reversed]
+    assert len(rev) == n_blocks, f"key_tiles_reversed: {len(rev)} flags for {n_blocks} Q blocks"
+    if all(rev) or not any(rev):
+        return None
+    return [i for i, r in enumerate(rev) if not r], [i for i, r in enumerate(rev) if r]
+
+
+def _by_direction(fn, split, q_blocks, Sq: int, BLOCK_M: int, row_args: dict, blk_args: dict, kw: dict, n_out: int):
+    """Run `fn` once per key-tile direction on the given Q blocks that walk that way (rows are independent) and put the
+    row-shaped results back in place.  row_args: arrays with the given rows on axis 2; blk_args: arrays with one entry per
+    given block on axis 2."""
+    nb = (Sq + BLOCK_M - 1) // BLOCK_M
+    blocks = list(range(nb)) if q_blocks is None else [int(b) for b in q_blocks]
+    outs = None
+    for pos, rev in zip(split, (False, True)):
+        lr = np.concatenate([np.arange(i * BLOCK_M, min((i + 1) * BLOCK_M, Sq)) for i in pos])
+        res = fn(**{k: a[:, :, lr] for k, a in row_args.items()}, **{k: a[:, :, pos] for k, a in blk_args.items()}, **kw,
+                 q_blocks=[blocks[i] for i in pos], key_tiles_reversed=rev)
+        res = res if isinstance(res, tuple) else (res,)
+        if outs is None:
+            outs = [None if r is None else np.zeros(r.shape[:2] + (Sq,) + r.shape[3:], r.dtype) for r in res[:n_out]]
+        for o, r in zip(outs, res):
+            if o is not None:
+                o[:, :, lr] = r
+    return tuple(outs)
+
+
+# --------------------------------------------------------------------------------------
 # L1: fused attention tile loop  (src/triton/attn_qk_int8_per_block{,_causal}.py)
 # --------------------------------------------------------------------------------------
 def attn_fwd_int8_fp16(q_i8, k_i8, v16, q_scale, k_scale, *, causal: bool, out_dtype: str = "fp16",
                        return_lse: bool = False, BLOCK_M: int = 128, BLOCK_N: int = 64,
-                       tail: str = "reference", pv_tile_fp16: bool = True, causal_mask: str = "reference"):
+                       tail: str = "reference", pv_tile_fp16: bool = True, causal_mask: str = "reference", q_blocks=None):
     """`_attn_fwd` + `_attn_fwd_inner` (src/triton/attn_qk_int8_per_block.py:69-167 / :24-66) and the
     causal pair (src/triton/attn_qk_int8_per_block_causal.py:82-214 / :24-79).
 
@@ -179,19 +235,22 @@ def attn_fwd_int8_fp16(q_i8, k_i8, v16, q_scale, k_scale, *, causal: bool, out_d
     `causal_mask`: 'reference' = the additive -1e6 of STAGE 2 (a key above the diagonal still takes part once scores reach
     ~1e6 binades, q, k of ~1000 N(0,1)); 'neg_inf' = masked with -inf, as the HIP kernels and the CUDA path do.  The two agree
     bit for bit while every score is far below 1e6 binades.
+    `q_blocks` (ascending block indices): the given Q rows are those 128-row blocks of a longer sequence, back to back (only the
+    last may be short: the ragged last block of the sequence), q_scale [B,Hq,len(q_blocks)] their scales.  The causal mask and
+    tile skipping use the absolute rows, so every row gets the bits of the same row of a full run.
     Rows are independent, so the loop runs over key tiles with all participating rows at once.
     Returns (o [B,Hq,Sq,D] fp32-valued rounded to out_dtype, lse [B,Hq,Sq] fp32 or None).
     """
     B, Hq, Sq, D = q_i8.shape
     _, Hkv, Sk, _ = k_i8.shape
     g = Hq // Hkv
+    rows = _rows_of_blocks(q_blocks, Sq, BLOCK_M)  # absolute row indices
     if causal:
-        assert Sq == Sk, "qo_len and kv_len must be equal for causal attention"  # causal :389
+        assert (Sq == Sk) if q_blocks is None else (rows[-1] < Sk), "qo_len and kv_len must be equal for causal attention"  # causal :389
     n_kt = (Sk + BLOCK_N - 1) // BLOCK_N
     o = np.zeros((B, Hq, Sq, D), np.float32)
     lse = np.zeros((B, Hq, Sq), np.float32) if return_lse else None
-    rows = np.arange(Sq)
-    row_blk = rows // BLOCK_M
+    row_blk = np.arange(Sq) // BLOCK_M  # index into the given scales
     for b in range(B):
         for h in range(Hq):
             hk = h // g
@@ -206,7 +265,8 @@ def attn_fwd_int8_fp16(q_i8, k_i8, v16, q_scale, k_scale, *, causal: bool, out_d
                 n0 = j * BLOCK_N
                 n1 = min(n0 + BLOCK_N, Sk)
                 if causal:
-                    r0 = (n0 // BLOCK_M) * BLOCK_M  # q-tiles m with m*128 <= n0 take part
+                    # q-tiles m with m*128 <= n0 take part: the given rows from the first one at or past that row on
+                    r0 = int(np.searchsorted(rows, (n0 // BLOCK_M) * BLOCK_M))
                     if r0 >= Sq:
                         break
                 else:
@@ -219,8 +279,8 @@ def attn_fwd_int8_fp16(q_i8, k_i8, v16, q_scale, k_scale, *, causal: bool, out_d
                 if n1 - n0 < BLOCK_N and tail == "neg_inf":
                     qk[:, n1 - n0:] = -np.inf
                 if causal:
-                    # rows of the diagonal q-tile (first BLOCK_M participating rows) are masked
-                    d1 = min(r0 + BLOCK_M, Sq)
+                    # rows of the diagonal q-tile (the given rows of block n0 // BLOCK_M) are masked
+                    d1 = int(np.searchsorted(rows, (n0 // BLOCK_M + 1) * BLOCK_M))
                     rr = rows[r0:d1, None]
                     cc = (n0 + np.arange(BLOCK_N))[None, :]
                     if causal_mask == "neg_inf":
@@ -268,7 +328,7 @@ def per_channel_fp8(v: np.ndarray):
 
 def attn_fwd_int8_fp8(q_i8, k_i8, v8, q_scale, k_scale, v_scale, *, causal: bool, out_dtype: str = "fp16",
                       return_lse: bool = False, BLOCK_M: int = 128, BLOCK_N: int = 64, return_slack: bool = False,
-                      key_tiles_reversed: bool = False):
+                      key_tiles_reversed=False, q_blocks=None):
     """`qk_int_sv_f8_attn_kernel` semantics (csrc/qattn/qk_int_sv_f8_cuda.cu:46-692) on per-block
     scales: p = exp2(s - m + 8.807) so that p_max = 448 (csrc/qattn/attn_utils.cuh:30,424-445);
     l += sum(p) in fp32 before the fp8 rounding (:314-317); p -> e4m3 satfinite RN
@@ -279,19 +339,29 @@ def attn_fwd_int8_fp8(q_i8, k_i8, v8, q_scale, k_scale, v_scale, *, causal: bool
     computed by the same code either way.
     `key_tiles_reversed` (non-causal only): walk the 64-key tiles from the last to the first, as the HIP kernel does for every
     other round of 64 Q blocks (L2 reuse).  P is rounded to e4m3 against the RUNNING row maximum, so the order changes which
-    references the codes are rounded against - by more than a rounding-boundary flip.
+    references the codes are rounded against - by more than a rounding-boundary flip.  One bool for the call, or one per given
+    Q block (the kernel's direction is a property of the block: `(qt // 64) & 1`).
+    `q_blocks`: the given rows are these Q blocks of a longer sequence, as in `attn_fwd_int8_fp16`.
     """
-    assert not (causal and key_tiles_reversed)
     B, Hq, Sq, D = q_i8.shape
+    split = _split_by_direction(q_blocks, q_scale.shape[2], key_tiles_reversed)
+    if split is not None:
+        kw = dict(k_i8=k_i8, v8=v8, k_scale=k_scale, v_scale=v_scale, causal=causal, out_dtype=out_dtype, return_lse=return_lse,
+                  BLOCK_M=BLOCK_M, BLOCK_N=BLOCK_N, return_slack=return_slack)
+        res = _by_direction(attn_fwd_int8_fp8, split, q_blocks, Sq, BLOCK_M, dict(q_i8=q_i8), dict(q_scale=q_scale), kw,
+                            3 if return_slack else 2)
+        return res
+    key_tiles_reversed = bool(np.all(key_tiles_reversed))
+    assert not (causal and key_tiles_reversed)
     _, Hkv, Sk, _ = k_i8.shape
     g = Hq // Hkv
+    rows = _rows_of_blocks(q_blocks, Sq, BLOCK_M)  # absolute row indices
     if causal:
-        assert Sq == Sk
+        assert (Sq == Sk) if q_blocks is None else (rows[-1] < Sk)
     n_kt = (Sk + BLOCK_N - 1) // BLOCK_N
     o = np.zeros((B, Hq, Sq, D), np.float32)
     lse = np.zeros((B, Hq, Sq), np.float32) if return_lse else None
-    rows = np.arange(Sq)
-    row_blk = rows // BLOCK_M
+    row_blk = np.arange(Sq) // BLOCK_M  # index into the given scales
     off = np.float32(FP8_P_OFFSET)
     for b in range(B):
         for h in range(Hq):
@@ -306,7 +376,7 @@ def attn_fwd_int8_fp8(q_i8, k_i8, v8, q_scale, k_scale, v_scale, *, causal: bool
             for j in (range(n_kt - 1, -1, -1) if key_tiles_reversed else range(n_kt)):
                 n0 = j * BLOCK_N
                 n1 = min(n0 + BLOCK_N, Sk)
-                r0 = (n0 // BLOCK_M) * BLOCK_M if causal else 0
+                r0 = int(np.searchsorted(rows, (n0 // BLOCK_M) * BLOCK_M)) if causal else 0
                 if r0 >= Sq:
                     break
                 qk = (qf[r0:] @ kf[n0:n1].T).astype(np.float32)
@@ -326,7 +396,7 @@ def attn_fwd_int8_fp8(q_i8, k_i8, v8, q_scale, k_scale, v_scale, *, causal: bool
                 lse[b, h] = np.log2(l_i) + m_i - off
     if return_slack:
         slack = fp8_flip_slack(q_i8, k_i8, v8, q_scale, k_scale, v_scale, o, causal=causal, BLOCK_M=BLOCK_M, BLOCK_N=BLOCK_N,
-                               key_tiles_reversed=key_tiles_reversed)
+                               key_tiles_reversed=key_tiles_reversed, q_blocks=q_blocks)
         return to_storage(o, out_dtype), lse, slack
     return to_storage(o, out_dtype), lse
 
@@ -385,7 +455,7 @@ def _grid_step(sc_max32: np.float32):
 
 
 def fp8_flip_slack(q_i8, k_i8, v8, q_scale, k_scale, v_scale, o, *, causal: bool, BLOCK_M: int = 128, BLOCK_N: int = 64,
-                   key_tiles_reversed: bool = False):
+                   key_tiles_reversed=False, q_blocks=None):
     """Per-element bound on |O_kernel - O_oracle| that comes from the e4m3 rounding of P (`attn_fwd_int8_fp8`, fp8-PV).
 
     P = e4m3(exp2(A)) has 3 mantissa bits: an argument that differs by a few fp32 ulps moves P across a rounding boundary
@@ -402,15 +472,21 @@ def fp8_flip_slack(q_i8, k_i8, v8, q_scale, k_scale, v_scale, o, *, causal: bool
         slack = (flip_acc / l) * v_scale + |o| * rowsum_acc / l
     i.e. the code flips moving the numerator, and a common factor 2^+-delta on P moving the row sum (this is what matters in
     one-hot rows, where the largest P saturates at 448 while l keeps the exact sum).  Everything else - fp32 accumulation
-    order, one output ulp - is left to the checker's rtol / atol.  Returns fp32 [B, Hq, Sq, D].
+    order, one output ulp - is left to the checker's rtol / atol.  `key_tiles_reversed` and `q_blocks` as in
+    `attn_fwd_int8_fp8`.  Returns fp32 [B, Hq, Sq, D].
     """
     B, Hq, Sq, D = q_i8.shape
+    split = _split_by_direction(q_blocks, q_scale.shape[2], key_tiles_reversed)
+    if split is not None:
+        kw = dict(k_i8=k_i8, v8=v8, k_scale=k_scale, v_scale=v_scale, causal=causal, BLOCK_M=BLOCK_M, BLOCK_N=BLOCK_N)
+        return _by_direction(fp8_flip_slack, split, q_blocks, Sq, BLOCK_M, dict(q_i8=q_i8, o=o), dict(q_scale=q_scale), kw, 1)[0]
+    key_tiles_reversed = bool(np.all(key_tiles_reversed))
     _, Hkv, Sk, _ = k_i8.shape
     g = Hq // Hkv
     n_kt = (Sk + BLOCK_N - 1) // BLOCK_N
     slack = np.zeros((B, Hq, Sq, D), np.float32)
-    rows = np.arange(Sq)
-    row_blk = rows // BLOCK_M
+    rows = _rows_of_blocks(q_blocks, Sq, BLOCK_M)  # absolute row indices
+    row_blk = np.arange(Sq) // BLOCK_M  # index into the given scales
     off = np.float32(FP8_P_OFFSET)
     with np.errstate(invalid="ignore", over="ignore"):
         for b in range(B):
@@ -436,7 +512,7 @@ def fp8_flip_slack(q_i8, k_i8, v8, q_scale, k_scale, v_scale, o, *, causal: bool
                 for j in (range(n_kt - 1, -1, -1) if key_tiles_reversed else range(n_kt)):
                     n0 = j * BLOCK_N
                     n1 = min(n0 + BLOCK_N, Sk)
-                    r0 = (n0 // BLOCK_M) * BLOCK_M if causal else 0
+                    r0 = int(np.searchsorted(rows, (n0 // BLOCK_M) * BLOCK_M)) if causal else 0
                     if r0 >= Sq:
                         break
                     R = slice(r0, Sq)
@@ -541,7 +617,7 @@ def lowbit_fa_forward(q, k, v, *, dtype: str = "fp16", tensor_layout: str = "HND
                       q_qmax: float = 127.0, k_qmax: float = 127.0, pv: str = "fp16",
                       tail: str = "reference", amax_floor: float = 0.0, pv_tile_fp16: bool = True,
                       return_intermediates: bool = False, return_slack: bool = False, causal_mask: str = "reference",
-                      fp8_key_tiles_reversed: bool = False):
+                      fp8_key_tiles_reversed=False, q_blocks=None):
     """`sageattn_qk_int8_pv_fp16_triton` (src/core.py:194-352); with q_qmax/k_qmax = 7 the intended
     semantics of `sageattn_qk_int4_pv_fp16_triton` (:945-1036, body defective - SURVEY 2.4-2/3); with
     pv='fp8' `sageattn_qk_int8_pv_fp8_cuda` (:735-941) on per-block scales.
@@ -551,6 +627,10 @@ def lowbit_fa_forward(q, k, v, *, dtype: str = "fp16", tensor_layout: str = "HND
     bf16 -> v.half() (:307-308); sm_scale = D_og^-0.5 (:309-310); quant (:311-320); attention
     (:321-342); slice (:343); lse/1.44269504 + lse_correction*sm_scale (:344-350).
     `return_slack` (pv='fp8' only): the e4m3 flip slack of O (`fp8_flip_slack`), laid out like o, is returned right after o.
+    `q_blocks` (ascending 128-row block indices): q holds only the rows of these Q blocks of a longer sequence, back to back
+    (`block_rows` gives them); k and v are whole.  km, the K / V codes and scales come from all keys, each Q block is quantised
+    on its own, the causal mask uses absolute rows: o, lse (and the slack) are the bits of the same rows of a full run.
+    `fp8_key_tiles_reversed`: one bool, or one per Q block (per given block with `q_blocks`).
     """
     if return_slack and pv != "fp8":
         raise ValueError("return_slack needs pv='fp8'")
@@ -573,12 +653,14 @@ def lowbit_fa_forward(q, k, v, *, dtype: str = "fp16", tensor_layout: str = "HND
                                                   amax_floor=amax_floor)
     if pv == "fp16":
         o, lse = attn_fwd_int8_fp16(q_i8, k_i8, v16, q_scale, k_scale, causal=is_causal, out_dtype=dtype,
-                                    return_lse=return_lse, tail=tail, pv_tile_fp16=pv_tile_fp16, causal_mask=causal_mask)
+                                    return_lse=return_lse, tail=tail, pv_tile_fp16=pv_tile_fp16, causal_mask=causal_mask,
+                                    q_blocks=q_blocks)
         v_scale = None
     elif pv == "fp8":
         v8, v_scale = per_channel_fp8(vc)
         res = attn_fwd_int8_fp8(q_i8, k_i8, v8, q_scale, k_scale, v_scale, causal=is_causal, out_dtype=dtype,
-                                return_lse=return_lse, return_slack=return_slack, key_tiles_reversed=fp8_key_tiles_reversed)
+                                return_lse=return_lse, return_slack=return_slack, key_tiles_reversed=fp8_key_tiles_reversed,
+                                q_blocks=q_blocks)
         o, lse = res[0], res[1]
         slack = res[2] if return_slack else None
     else:
@@ -671,11 +753,13 @@ def make_varlen_inputs(lens_q, lens_k, Hq, Hkv, D, *, seed=0, dtype="fp16", k_bi
 # --------------------------------------------------------------------------------------
 # CPU baseline: the repo's naive SDPA  (src/core.py:46-69)
 # --------------------------------------------------------------------------------------
-def sdpa_naive(q, k, v, is_causal: bool = False, sm_scale=None, return_lse: bool = False):
+def sdpa_naive(q, k, v, is_causal: bool = False, sm_scale=None, return_lse: bool = False, q_blocks=None):
     """`manual_scaled_dot_product_attention` (src/core.py:46-69) with the intended K^T
     (`transpose([0,1,3,2])`; the reference's `[0,2,3,1]` at :55 is a bug):
     scores = q.k^T * D^-0.5 (:55); causal: scores += (1 - tril) * -1e9 (:58-61); softmax (:64); @ v (:67).
-    Canonical [B,H,S,D]; GQA handled by repeating kv heads.  fp32 math (float64 when inputs are)."""
+    Canonical [B,H,S,D]; GQA handled by repeating kv heads.  fp32 math (float64 when inputs are).
+    `q_blocks`: q holds only the rows of these 128-row Q blocks of a longer sequence (as in `lowbit_fa_forward`); the causal
+    mask uses their absolute rows."""
     B, Hq, Sq, D = q.shape
     Hkv = k.shape[1]
     if Hkv != Hq:
@@ -685,7 +769,10 @@ def sdpa_naive(q, k, v, is_causal: bool = False, sm_scale=None, return_lse: bool
     scores = np.matmul(q, np.swapaxes(k, -1, -2)) * q.dtype.type(scale)
     if is_causal:
         Sk = scores.shape[-1]
-        mask = np.tril(np.ones((Sq, Sk), dtype=scores.dtype))
+        if q_blocks is None:
+            mask = np.tril(np.ones((Sq, Sk), dtype=scores.dtype))
+        else:
+            mask = (_rows_of_blocks(q_blocks, Sq)[:, None] >= np.arange(Sk)[None, :]).astype(scores.dtype)
         scores = scores + (1 - mask) * q.dtype.type(-1e9)
     mx = scores.max(axis=-1, keepdims=True)
     e = np.exp(scores - mx)
