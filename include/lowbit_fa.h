@@ -200,6 +200,39 @@ int lbfa_sdpa_fwd(const void* q, const void* k, const void* v, int dtype, void* 
                   const int64_t strides_o[3], double sm_scale, int is_causal, void* stream);
 
 /*
+ * Attention backward: dq, dk, dv of the dense operators (lbfa_forward with pv_fp8 = 0 or 1, and lbfa_sdpa_fwd).  Additive to
+ * ABI 200 (LBFA_VERSION unchanged): callers detect it by looking up the symbol.
+ *   Straight-through on the quantiser: P is the forward's own P, recomputed from the scores the forward used (the int8 /
+ *   int4-range codes x q_scale x k_scale, regenerated bit for bit by the forward's mean and quantiser kernels; or the 16-bit
+ *   Q K^T * sm_scale when q_qmax = 0) and from the LSE the forward returned: P = exp2(s2 - lse2), lse2 = (lse - dtype(q . km)
+ *   * sm_scale) * log2(e) (the smooth-K correction of src/core.py:344-350 is taken out again).  With the fp8-PV operator that is
+ *   the fp32 P before its e4m3 rounding.  The gradient products use the un-quantised 16-bit tensors (fp16 / bf16 MFMA, fp32
+ *   accumulation) and the ORIGINAL K (not K - km):
+ *     dV = P^T dO,  dP = dO V^T,  delta_i = sum_d dO_id O_id - dLSE_i,  dS = P o (dP - delta),
+ *     dQ = sm_scale dS K,  dK = sm_scale dS^T Q;   GQA: dk / dv of a kv head sum over its Hq / Hkv query heads.
+ *   Causal, keys >= Sk and queries >= Sq are masked as in the forward.  No float atomics: every sum is formed in one fixed
+ *   order, results are bitwise reproducible run to run.
+ *   q, k, v, o, dout : fp16 / bf16 (dtype), 16-byte aligned, strides {batch, head, seq} multiples of 8 elements; o is the
+ *                      forward's output, dout the upstream gradient of o.
+ *   lse  : [B,Hq,Sq] contiguous fp32, the NATURAL-log LSE the forward returned (lbfa_forward / lbfa_sdpa_fwd with lse != NULL).
+ *   dlse : NULL, or [B,Hq,Sq] contiguous fp32 upstream gradient of lse.
+ *   dq / dk / dv : outputs in dtype, shaped like q / k / v, any element strides.
+ *   D    : 64 or 128 (pad other head dims with zeros, as the forward's results are those of the zero-padded tensors).
+ *   sm_scale, q_qmax, k_qmax, is_causal, smooth_k : the forward's arguments; q_qmax = k_qmax = 0 selects the un-quantised
+ *          scores of lbfa_sdpa_fwd (smooth_k is then ignored).
+ *   workspace: >= lbfa_backward_workspace_bytes(B, Hq, Hkv, Sq, Sk, D, q_qmax, smooth_k) bytes, 16-byte aligned; contents
+ *          undefined afterwards.  Every argument is checked before the first launch (LBFA_EINVAL: nothing enqueued).
+ */
+size_t lbfa_backward_workspace_bytes(int B, int Hq, int Hkv, int Sq, int Sk, int D, int q_qmax, int smooth_k);
+int lbfa_backward(const void* q, const void* k, const void* v, const void* o, const void* dout, int dtype, const float* lse,
+                  const float* dlse, void* dq, void* dk, void* dv, void* workspace, size_t workspace_bytes,
+                  int B, int Hq, int Hkv, int Sq, int Sk, int D,
+                  const int64_t strides_q[3], const int64_t strides_k[3], const int64_t strides_v[3], const int64_t strides_o[3],
+                  const int64_t strides_dout[3], const int64_t strides_dq[3], const int64_t strides_dk[3],
+                  const int64_t strides_dv[3], double sm_scale, int q_qmax, int k_qmax, int is_causal, int smooth_k,
+                  void* stream);
+
+/*
  * Packed variable-length batches (reference: `sageattn_varlen`, src/core.py:356-491).
  *   q [total_q, Hq, D], k / v [total_k, Hkv, D]; sequence b owns tokens [cu_seqlens[b], cu_seqlens[b+1]);
  *   cu_seqlens_* are int32 device arrays of B + 1 entries; strides are in elements {head, token}.

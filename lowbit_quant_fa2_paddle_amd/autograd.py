@@ -1,0 +1,78 @@
+"""Autograd for the dense attention operators (torch only): a `torch.autograd.Function` whose forward is the operator's own
+forward (the same `lbfa_forward` / `lbfa_sdpa_fwd` call, with an LSE buffer) and whose backward is one `lbfa_backward` call.
+
+Straight-through on the quantiser: the backward recomputes the forward's own P from the same codes and scales and from the
+returned LSE, and forms dq, dk, dv from the un-quantised 16-bit q, k, v (include/lowbit_fa.h, DESIGN.md "Backward").
+The operators route here only when grad mode is on and q, k or v requires grad; every other call takes the unchanged path.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+from . import quant_per_block as _qpb
+
+
+def _kernel_operand(t, D):
+    """last-dim contiguous, zero-padded to D channels, 16-byte aligned with strides that are multiples of 8 elements"""
+    if t.stride(-1) != 1:
+        t = t.contiguous()
+    if t.shape[-1] != D:
+        t = F.pad(t, (0, D - t.shape[-1]))
+    if t.data_ptr() % 16 or any(s % 8 for s in t.stride()[:3]):
+        t = t.contiguous()
+    return t
+
+
+class _AttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, forward, cfg):
+        # runs with grad mode off: `forward` takes the operator's plain path
+        o, lse = forward(q, k, v)
+        ctx.cfg = cfg
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(q, k, v, o, lse)
+        return o, lse
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, do, dlse):
+        q, k, v, o, lse = ctx.saved_tensors
+        layout, is_causal, sm_scale, smooth_k, q_qmax, k_qmax = ctx.cfg
+        if do is None and dlse is None:
+            return None, None, None, None, None
+        if do is None:
+            do = torch.zeros_like(o)
+        Dg = q.shape[-1]
+        D = 64 if Dg <= 64 else 128
+        qp, kp, vp, op, dop = (_kernel_operand(t, D) for t in (q, k, v, o, do.to(o.dtype)))
+        dq = torch.empty(qp.shape, dtype=q.dtype, device=q.device)
+        dk = torch.empty(kp.shape, dtype=k.dtype, device=k.device)
+        dv = torch.empty(vp.shape, dtype=v.dtype, device=v.device)
+        (B, Hq, Sq), _ = _qpb._bhs(qp.shape, qp.stride(), layout)
+        (_, Hkv, Sk), _ = _qpb._bhs(kp.shape, kp.stride(), layout)
+        st = lambda t: _lib.strides3(_qpb._bhs(t.shape, t.stride(), layout)[1])
+        if dlse is not None:
+            dlse = dlse.to(torch.float32).contiguous()
+        lib = _lib.load()
+        ws_bytes = lib.lbfa_backward_workspace_bytes(B, Hq, Hkv, Sq, Sk, D, q_qmax, 1 if smooth_k else 0)
+        ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=q.device)
+        code = _lib.LBFA_F16 if q.dtype == torch.float16 else _lib.LBFA_BF16
+        with torch.cuda.device(q.device):
+            _lib.check(lib.lbfa_backward(qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), op.data_ptr(), dop.data_ptr(), code,
+                                         lse.data_ptr(), dlse.data_ptr() if dlse is not None else None,
+                                         dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ws.data_ptr(), ws_bytes,
+                                         B, Hq, Hkv, Sq, Sk, D, st(qp), st(kp), st(vp), st(op), st(dop), st(dq), st(dk), st(dv),
+                                         float(sm_scale), int(q_qmax), int(k_qmax), 1 if is_causal else 0,
+                                         1 if smooth_k else 0, torch.cuda.current_stream(q.device).cuda_stream), lib)
+        if D != Dg:
+            dq, dk, dv = dq[..., :Dg], dk[..., :Dg], dv[..., :Dg]
+        return dq, dk, dv, None, None
+
+
+def attention(q, k, v, forward, *, tensor_layout, is_causal, sm_scale, smooth_k, q_qmax, k_qmax):
+    """(o, lse) of `forward(q, k, v)` (the operator with return_lse=True) with a backward through `lbfa_backward`.
+    q_qmax = k_qmax = 0: un-quantised scores (flash_attn_fp16)."""
+    return _AttentionFn.apply(q, k, v, forward, (tensor_layout, is_causal, float(sm_scale), bool(smooth_k), q_qmax, k_qmax))

@@ -37,6 +37,20 @@ def _check_inputs(q, k, v):
     return ops, dtype
 
 
+def _wants_grad(ops, q, k, v) -> bool:
+    """grad mode on and q, k or v requires grad (torch): the call goes through autograd.py; otherwise the plain path runs"""
+    return ops.name == "torch" and ops.torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad)
+
+
+def _differentiable(q, k, v, forward, *, tensor_layout, is_causal, sm_scale, smooth_k, return_lse, q_qmax, k_qmax):
+    from . import autograd as _ag
+    if sm_scale is None:
+        sm_scale = 1.0 / q.shape[-1] ** 0.5
+    o, lse = _ag.attention(q, k, v, lambda a, b, c: forward(a, b, c, sm_scale), tensor_layout=tensor_layout,
+                           is_causal=is_causal, sm_scale=sm_scale, smooth_k=smooth_k, q_qmax=q_qmax, k_qmax=k_qmax)
+    return (o, lse) if return_lse else o
+
+
 def _pad_head_dim(ops, q, k, v):
     head_dim_og = ops.shape(q)[-1]
     if head_dim_og < 64:
@@ -74,6 +88,11 @@ def _low_bit_attention(q, k, v, *, tensor_layout, is_causal, sm_scale, smooth_k,
         return o
     if 0 in kshape:
         raise ValueError("k/v must hold at least one key (softmax over an empty set is undefined)")
+    if _wants_grad(ops, q, k, v):
+        fwd = lambda a, b, c, scale: _low_bit_attention(a, b, c, tensor_layout=tensor_layout, is_causal=is_causal, sm_scale=scale,
+                                                        smooth_k=smooth_k, return_lse=True, q_qmax=q_qmax, k_qmax=k_qmax, pv=pv)
+        return _differentiable(q, k, v, fwd, tensor_layout=tensor_layout, is_causal=is_causal, sm_scale=sm_scale,
+                               smooth_k=smooth_k, return_lse=return_lse, q_qmax=q_qmax, k_qmax=k_qmax)
     q, k, v, head_dim_og = _pad_head_dim(ops, q, k, v)
     if sm_scale is None:
         sm_scale = 1.0 / head_dim_og ** 0.5  # ORIGINAL head dim (:309-310)
@@ -253,6 +272,11 @@ def flash_attn_fp16(q, k, v, tensor_layout: str = "HND", is_causal: bool = False
         return (o, ops.empty((qshape[0], qshape[hdim], qshape[3 - hdim]), ops.float32, q)) if return_lse else o
     if 0 in ops.shape(k):
         raise ValueError("k/v must hold at least one key (softmax over an empty set is undefined)")
+    if _wants_grad(ops, q, k, v):
+        fwd = lambda a, b, c, scale: flash_attn_fp16(a, b, c, tensor_layout=tensor_layout, is_causal=is_causal, sm_scale=scale,
+                                                     return_lse=True)
+        return _differentiable(q, k, v, fwd, tensor_layout=tensor_layout, is_causal=is_causal, sm_scale=sm_scale,
+                               smooth_k=False, return_lse=return_lse, q_qmax=0, k_qmax=0)
     q, k, v, head_dim_og = _pad_head_dim(ops, q, k, v)
     if sm_scale is None:
         sm_scale = 1.0 / head_dim_og ** 0.5

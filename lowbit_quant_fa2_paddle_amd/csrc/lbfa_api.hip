@@ -21,6 +21,8 @@ hipError_t launch_attn_fwd_qq(const AttnParams& p, int D, int dtype, int v_dtype
 hipError_t launch_cast_bf16_f16(const void* src, void* dst, int B, int H, int S, int d_valid, const int64_t* ss, const int64_t* ds,
                                 hipStream_t stream);
 hipError_t launch_absmax(const void* x, int dtype, float* out, int B, int H, int S, int D, const int64_t* st, hipStream_t stream);
+// defined in attn_bwd.hip
+hipError_t launch_attn_bwd(const BwdParams& p, int dtype, bool quant, bool causal, hipStream_t stream);
 }  // namespace lbfa
 
 namespace {
@@ -673,6 +675,130 @@ int lbfa_forward_varlen(const void* q, const void* k, const void* v, int dtype, 
   return attn_varlen_core("lbfa_forward_varlen", (const int8_t*)q, k8, v_in, v_dtype, o, dtype, nullptr, ks, cu_seqlens_q, cu_seqlens_k,
                           nullptr, nullptr, B, Hq, Hkv, max_seqlen_q, max_seqlen_k, D, Dg, strides_q, sk8, sv, strides_o,
                           is_causal, stream, true, (float)(sm_scale * 1.44269504), q_qmax);
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------
+// backward (attn_bwd.hip): straight-through on the quantiser, deterministic two-kernel FlashAttention-2 form
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+struct BwdLayout {
+  size_t km, part, q8, qs, k8, ks, corr, lse2, delta, total;
+};
+BwdLayout bwd_layout(int B, int Hq, int Hkv, int Sq, int Sk, int D, int quant, int smooth_k) {
+  BwdLayout L;
+  size_t o = 0;
+  auto take = [&](size_t n) { size_t at = o; o += align256(n); return at; };
+  const bool sm = quant && smooth_k;
+  L.km = take(sm ? (size_t)B * Hkv * D * 2 : 0);
+  L.part = take(sm ? lbfa_mean_seq_workspace_bytes(B, Hkv, Sk, D) : 0);
+  L.q8 = take(quant ? (size_t)B * Hq * Sq * D : 0);
+  L.qs = take(quant ? (size_t)B * Hq * ((Sq + LBFA_BLKQ - 1) / LBFA_BLKQ) * 4 : 0);
+  L.k8 = take(quant ? (size_t)B * Hkv * Sk * D : 0);
+  L.ks = take(quant ? (size_t)B * Hkv * ((Sk + LBFA_BLKK - 1) / LBFA_BLKK) * 4 : 0);
+  L.corr = take(sm ? (size_t)B * Hq * Sq * 4 : 0);
+  L.lse2 = take((size_t)B * Hq * Sq * 4);
+  L.delta = take((size_t)B * Hq * Sq * 4);
+  L.total = o;
+  return L;
+}
+bool strides8(const int64_t s[3]) { return (s[0] | s[1] | s[2]) % 8 == 0; }
+}  // namespace
+
+size_t lbfa_backward_workspace_bytes(int B, int Hq, int Hkv, int Sq, int Sk, int D, int q_qmax, int smooth_k) {
+  if (B <= 0 || Hq <= 0 || Hkv <= 0 || Sq <= 0 || Sk <= 0 || (D != 64 && D != 128)) return 0;
+  return bwd_layout(B, Hq, Hkv, Sq, Sk, D, q_qmax != 0, smooth_k).total;
+}
+
+int lbfa_backward(const void* q, const void* k, const void* v, const void* o, const void* dout, int dtype, const float* lse,
+                  const float* dlse, void* dq, void* dk, void* dv, void* workspace, size_t workspace_bytes,
+                  int B, int Hq, int Hkv, int Sq, int Sk, int D,
+                  const int64_t strides_q[3], const int64_t strides_k[3], const int64_t strides_v[3], const int64_t strides_o[3],
+                  const int64_t strides_dout[3], const int64_t strides_dq[3], const int64_t strides_dk[3],
+                  const int64_t strides_dv[3], double sm_scale, int q_qmax, int k_qmax, int is_causal, int smooth_k,
+                  void* stream) {
+  // every check before the first launch: LBFA_EINVAL means nothing was enqueued
+  if (!q || !k || !v || !o || !dout || !lse || !dq || !dk || !dv || !workspace || !strides_q || !strides_k || !strides_v ||
+      !strides_o || !strides_dout || !strides_dq || !strides_dk || !strides_dv)
+    return fail(LBFA_EINVAL, "lbfa_backward: null pointer");
+  if (B <= 0 || Hq <= 0 || Hkv <= 0 || Sq <= 0 || Sk <= 0) return fail(LBFA_EINVAL, "lbfa_backward: empty tensor");
+  if (D != 64 && D != 128) return fail(LBFA_EINVAL, "lbfa_backward: Unsupported head_dim: %d (64 or 128; pad other head dims with zeros)", D);
+  if (Hq % Hkv != 0) return fail(LBFA_EINVAL, "num_qo_heads (%d) must be divisible by num_kv_heads (%d)", Hq, Hkv);
+  if (dtype != LBFA_F16 && dtype != LBFA_BF16) return fail(LBFA_EINVAL, "Input tensors must be in dtype of float16 or bfloat16");
+  if ((q_qmax != 0 && q_qmax != 7 && q_qmax != 127) || (k_qmax != 0 && k_qmax != 7 && k_qmax != 127) || ((q_qmax == 0) != (k_qmax == 0)))
+    return fail(LBFA_EINVAL, "lbfa_backward: q_qmax / k_qmax must both be 0 (un-quantised) or each 127 / 7, got %d / %d", q_qmax, k_qmax);
+  if (is_causal && Sq != Sk) return fail(LBFA_EINVAL, "qo_len and kv_len must be equal for causal attention");
+  if (!(sm_scale > 0.0)) return fail(LBFA_EINVAL, "lbfa_backward: sm_scale must be positive");
+  const void* in16[5] = {q, k, v, o, dout};
+  const int64_t* st16[5] = {strides_q, strides_k, strides_v, strides_o, strides_dout};
+  const char* nm16[5] = {"q", "k", "v", "o", "dout"};
+  for (int i = 0; i < 5; ++i)
+    if (!aligned16(in16[i]) || !strides8(st16[i]))
+      return fail(LBFA_EINVAL, "lbfa_backward: %s must be 16-byte aligned with strides that are multiples of 8 elements", nm16[i]);
+  if ((reinterpret_cast<uintptr_t>(dq) | reinterpret_cast<uintptr_t>(dk) | reinterpret_cast<uintptr_t>(dv)) & 1u)
+    return fail(LBFA_EINVAL, "lbfa_backward: dq / dk / dv must be 2-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(lse) | reinterpret_cast<uintptr_t>(dlse)) & 3u)
+    return fail(LBFA_EINVAL, "lbfa_backward: lse / dlse must be 4-byte aligned");
+  const int quant = q_qmax != 0, sm = quant && smooth_k;
+  const BwdLayout L = bwd_layout(B, Hq, Hkv, Sq, Sk, D, quant, smooth_k);
+  if (workspace_bytes < L.total) return fail(LBFA_EINVAL, "lbfa_backward: workspace too small (%zu < %zu)", workspace_bytes, L.total);
+  if (!aligned16(workspace)) return fail(LBFA_EINVAL, "lbfa_backward: workspace must be 16-byte aligned");
+  const int nkb = (Sk + 63) / 64, nqb = (Sq + 63) / 64;
+  if ((int64_t)B * Hq * Sq > 0x7fffffffLL || (int64_t)B * Hq * nqb > 0x7fffffffLL || (int64_t)B * Hkv * nkb > 0x7fffffffLL)
+    return fail(LBFA_EINVAL, "lbfa_backward: grid too large");
+
+  char* ws = (char*)workspace;
+  lbfa::BwdParams p;
+  p.q8 = p.k8 = nullptr;
+  p.q_scale = p.k_scale = nullptr;
+  p.corr = nullptr;
+  p.q8b = p.q8h = p.q8s = p.k8b = p.k8h = p.k8s = 0;
+  int st;
+  if (quant) {
+    // the forward's codes, bit for bit: the same mean and quantiser kernels (lbfa_forward quantises Q inside its attention
+    // kernel with this arithmetic, and fuses the last step of the mean into the K quantiser in the same order)
+    void* km = sm ? (void*)(ws + L.km) : nullptr;
+    int8_t* q8 = (int8_t*)(ws + L.q8);
+    int8_t* k8 = (int8_t*)(ws + L.k8);
+    const int64_t sq8[3] = {(int64_t)Hq * Sq * D, (int64_t)Sq * D, D}, sk8[3] = {(int64_t)Hkv * Sk * D, (int64_t)Sk * D, D};
+    if (sm) {
+      st = mean_impl(k, dtype, km, ws + L.part, lbfa_mean_seq_workspace_bytes(B, Hkv, Sk, D), B, Hkv, Sk, D, D, strides_k, stream);
+      if (st) return st;
+    }
+    st = quant_impl(k, dtype, km, 1, k8, (float*)(ws + L.ks), 1.0f, k_qmax, LBFA_BLKK, B, Hkv, Sk, D, D, strides_k, sk8, nullptr, 1,
+                    nullptr, stream);
+    if (st) return st;
+    st = quant_impl(q, dtype, nullptr, 1, q8, (float*)(ws + L.qs), (float)(sm_scale * 1.44269504), q_qmax, LBFA_BLKQ, B, Hq, Sq, D, D,
+                    strides_q, sq8, km, Hq / Hkv, sm ? (float*)(ws + L.corr) : nullptr, stream);
+    if (st) return st;
+    p.q8 = q8; p.k8 = k8;
+    p.q_scale = (const float*)(ws + L.qs); p.k_scale = (const float*)(ws + L.ks);
+    p.corr = sm ? (const float*)(ws + L.corr) : nullptr;
+    p.q8b = sq8[0]; p.q8h = sq8[1]; p.q8s = sq8[2];
+    p.k8b = sk8[0]; p.k8h = sk8[1]; p.k8s = sk8[2];
+  }
+  p.q = (const unsigned short*)q; p.k = (const unsigned short*)k; p.v = (const unsigned short*)v;
+  p.o = (const unsigned short*)o; p.dout = (const unsigned short*)dout;
+  p.dq = (unsigned short*)dq; p.dk = (unsigned short*)dk; p.dv = (unsigned short*)dv;
+  p.lse = lse; p.dlse = dlse;
+  p.lse2 = (float*)(ws + L.lse2); p.delta = (float*)(ws + L.delta);
+  p.qb = strides_q[0]; p.qh = strides_q[1]; p.qs = strides_q[2];
+  p.kb = strides_k[0]; p.kh = strides_k[1]; p.ks = strides_k[2];
+  p.vb = strides_v[0]; p.vh = strides_v[1]; p.vs = strides_v[2];
+  p.ob = strides_o[0]; p.oh = strides_o[1]; p.os = strides_o[2];
+  p.db = strides_dout[0]; p.dh = strides_dout[1]; p.ds = strides_dout[2];
+  p.dqb = strides_dq[0]; p.dqh = strides_dq[1]; p.dqs = strides_dq[2];
+  p.dkb = strides_dk[0]; p.dkh = strides_dk[1]; p.dks = strides_dk[2];
+  p.dvb = strides_dv[0]; p.dvh = strides_dv[1]; p.dvs = strides_dv[2];
+  p.B = B; p.Hq = Hq; p.Hkv = Hkv; p.Sq = Sq; p.Sk = Sk; p.D = D;
+  p.nQ = (Sq + LBFA_BLKQ - 1) / LBFA_BLKQ;
+  p.nK = (Sk + LBFA_BLKK - 1) / LBFA_BLKK;
+  p.group = Hq / Hkv;
+  p.sm_scale = (float)sm_scale;
+  p.qk_scale = (float)(sm_scale * 1.44269504);  // as lbfa_sdpa_fwd
+  p.corr_scale = (float)sm_scale;               // as lbfa_forward's LSE fix-up
+  g_err[0] = 0;
+  return check_hip(lbfa::launch_attn_bwd(p, dtype, quant != 0, is_causal != 0, (hipStream_t)stream), "lbfa_backward launch");
 }
 
 }  // extern "C"

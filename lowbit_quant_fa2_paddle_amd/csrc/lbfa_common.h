@@ -145,4 +145,22 @@ struct AttnParams {
   const unsigned short* q_dot_vec;
 };
 
+// attention backward (attn_bwd.hip); strides in elements {batch, head, seq}, last dim contiguous, D in {64, 128}
+struct BwdParams {
+  const unsigned short *q, *k, *v, *o, *dout;  // fp16 / bf16 inputs
+  unsigned short *dq, *dk, *dv;                // gradients, same dtype
+  const int8_t *q8, *k8;                       // forward's codes (quantised operators) or null
+  const float *q_scale, *k_scale;              // [B,Hq,nQ] / [B,Hkv,nK] contiguous
+  const float* lse;    // [B,Hq,Sq] natural-log LSE as the forward returned it
+  const float* dlse;   // [B,Hq,Sq] or null
+  const float* corr;   // smooth-K correction q . km [B,Hq,Sq] (storage-dtype rounded) or null
+  float *lse2, *delta; // [B,Hq,Sq] workspace: base-2 LSE without the correction, rowsum(dO o O) - dLSE
+  int64_t qb, qh, qs, kb, kh, ks, vb, vh, vs, ob, oh, os, db, dh, ds;
+  int64_t dqb, dqh, dqs, dkb, dkh, dks, dvb, dvh, dvs, q8b, q8h, q8s, k8b, k8h, k8s;
+  int B, Hq, Hkv, Sq, Sk, D, nQ, nK, group;
+  float sm_scale;    // natural-log softmax scale: dQ = sm_scale dS K, dK = sm_scale dS^T Q
+  float qk_scale;    // un-quantised scores: sm_scale * log2(e)
+  float corr_scale;  // sm_scale (multiplies corr)
+};
+
 }  // namespace lbfa
