@@ -252,7 +252,8 @@ int lbfa_backward(const void* q, const void* k, const void* v, const void* o, co
  *
  * lbfa_forward_varlen = the whole operator in one call (mean over all tokens, both quantisers, attention) on a
  * caller-owned workspace of lbfa_forward_varlen_workspace_bytes(...) bytes; internally the scales use a padded
- * [B, H, max_blocks] layout, so no cu_seqlens_scale tables are needed.
+ * [B, H, max_blocks] layout, so no cu_seqlens_scale tables are needed.  lbfa_forward_varlen_lse adds the LSE and
+ * lbfa_backward_varlen the gradients (below).
  */
 int lbfa_quant_per_block_varlen(const void* x, int dtype, const void* mean, int mean_group, int8_t* out, float* scale,
                                 const int32_t* cu_seqlens, const int32_t* cu_seqlens_scale, float sm_scale, int qmax,
@@ -274,6 +275,48 @@ int lbfa_forward_varlen(const void* q, const void* k, const void* v, int dtype, 
                         const int64_t strides_q[2], const int64_t strides_k[2], const int64_t strides_v[2],
                         const int64_t strides_o[2], double sm_scale, int q_qmax, int k_qmax, int is_causal, int smooth_k,
                         void* stream);
+
+/*
+ * lbfa_forward_varlen with an LSE (additive to ABI 200, LBFA_VERSION unchanged).  Same arguments and workspace query, `o` bit
+ * for bit what lbfa_forward_varlen writes, plus
+ *   lse : NULL (exactly lbfa_forward_varlen) or [Hq, total_q] contiguous fp32, 4-byte aligned - the layout of FlashAttention-2's
+ *         varlen softmax_lse.  Row (h, cu_seqlens_q[b] + i) is the natural-log LSE of query i of sequence b, defined as
+ *         lbfa_forward defines it: lse2 / log2(e) + dtype(q . km) * sm_scale with km the ONE mean over all packed keys.  Rows
+ *         of a sequence with no keys get -inf; rows in no sequence, or past max_seqlen_q in theirs, are not written.
+ */
+int lbfa_forward_varlen_lse(const void* q, const void* k, const void* v, int dtype, void* o, float* lse,
+                            const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, void* workspace, size_t workspace_bytes,
+                            int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D,
+                            const int64_t strides_q[2], const int64_t strides_k[2], const int64_t strides_v[2],
+                            const int64_t strides_o[2], double sm_scale, int q_qmax, int k_qmax, int is_causal, int smooth_k,
+                            void* stream);
+
+/*
+ * Backward of lbfa_forward_varlen (additive to ABI 200): the contract of lbfa_backward applied sequence by sequence.  Sequence b
+ * owns query tokens [cu_seqlens_q[b], cu_seqlens_q[b+1]) and key tokens [cu_seqlens_k[b], cu_seqlens_k[b+1]), cut at
+ * max_seqlen_q / max_seqlen_k as in the forward; no gradient crosses a sequence boundary.  P is rebuilt from the forward's codes
+ * (km over all total_k keys, K by the forward's quantiser, Q as the attention kernel quantises it in-kernel) and from its LSE.
+ *   q, k, v, o, dout : as lbfa_forward_varlen's tensors (o its output, dout the upstream gradient), 16-byte aligned, strides
+ *                      {head, token} multiples of 8 elements.
+ *   lse / dlse : [Hq, total_q] fp32 (lbfa_forward_varlen_lse's lse; dlse NULL or its upstream gradient).
+ *   dq / dk / dv : outputs in dtype, shaped like q / k / v, strides {head, token}.  Written completely: tokens in no sequence or
+ *                  past the cut get zeros, a query whose sequence has no keys gets dq = 0, keys of a sequence with no queries
+ *                  get dk = dv = 0.
+ *   q_qmax, k_qmax : 127 or 7 each (the varlen forward has no un-quantised mode).  D : 64 or 128 (the caller pads).
+ *   Causal assumes len_q == len_k per sequence (unchecked: cu_seqlens stay on the device).  No float atomics: bitwise
+ *   reproducible.  workspace: >= lbfa_backward_varlen_workspace_bytes(...) bytes, 16-byte aligned.  Every argument is checked
+ *   before the first launch.
+ */
+size_t lbfa_backward_varlen_workspace_bytes(int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k,
+                                            int D, int q_qmax, int smooth_k);
+int lbfa_backward_varlen(const void* q, const void* k, const void* v, const void* o, const void* dout, int dtype, const float* lse,
+                         const float* dlse, void* dq, void* dk, void* dv, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k,
+                         void* workspace, size_t workspace_bytes, int B, int Hq, int Hkv, int total_q, int total_k,
+                         int max_seqlen_q, int max_seqlen_k, int D,
+                         const int64_t strides_q[2], const int64_t strides_k[2], const int64_t strides_v[2], const int64_t strides_o[2],
+                         const int64_t strides_dout[2], const int64_t strides_dq[2], const int64_t strides_dk[2],
+                         const int64_t strides_dv[2], double sm_scale, int q_qmax, int k_qmax, int is_causal, int smooth_k,
+                         void* stream);
 
 #ifdef __cplusplus
 }

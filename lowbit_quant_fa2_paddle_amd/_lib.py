@@ -66,6 +66,15 @@ SIGNATURES = {
                                   ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
                                   ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
                                   _cd, _ci, _ci, _ci, _ci, _vp]),
+    "lbfa_forward_varlen_lse": (_ci, [_vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _sz,
+                                      _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci,
+                                      ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                      ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                      _cd, _ci, _ci, _ci, _ci, _vp]),
+    "lbfa_backward_varlen_workspace_bytes": (_sz, [_ci] * 10),
+    "lbfa_backward_varlen": (_ci, [_vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                   _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci] + [ctypes.POINTER(ctypes.c_int64)] * 8 +
+                                  [_cd, _ci, _ci, _ci, _ci, _vp]),
 }
 
 _lock = threading.Lock()

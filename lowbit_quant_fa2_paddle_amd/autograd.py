@@ -1,5 +1,6 @@
-"""Autograd for the dense attention operators (torch only): a `torch.autograd.Function` whose forward is the operator's own
-forward (the same `lbfa_forward` / `lbfa_sdpa_fwd` call, with an LSE buffer) and whose backward is one `lbfa_backward` call.
+"""Autograd for the attention operators (torch only): a `torch.autograd.Function` whose forward is the operator's own forward
+(the same `lbfa_forward` / `lbfa_sdpa_fwd` call, with an LSE buffer) and whose backward is one `lbfa_backward` call; for packed
+batches (`sageattn_varlen`) the same with `lbfa_forward_varlen_lse` and `lbfa_backward_varlen`.
 
 Straight-through on the quantiser: the backward recomputes the forward's own P from the same codes and scales and from the
 returned LSE, and forms dq, dk, dv from the un-quantised 16-bit q, k, v (include/lowbit_fa.h, DESIGN.md "Backward").
@@ -76,3 +77,60 @@ def attention(q, k, v, forward, *, tensor_layout, is_causal, sm_scale, smooth_k,
     """(o, lse) of `forward(q, k, v)` (the operator with return_lse=True) with a backward through `lbfa_backward`.
     q_qmax = k_qmax = 0: un-quantised scores (flash_attn_fp16)."""
     return _AttentionFn.apply(q, k, v, forward, (tensor_layout, is_causal, float(sm_scale), bool(smooth_k), q_qmax, k_qmax))
+
+
+class _VarlenAttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, cu_q, cu_k, forward, cfg):
+        # runs with grad mode off: `forward` takes the plain packed path with an LSE [Hq, total_q]
+        o, lse = forward(q, k, v)
+        ctx.cfg = cfg
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(q, k, v, o, lse, cu_q, cu_k)
+        return o, lse
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, do, dlse):
+        q, k, v, o, lse, cu_q, cu_k = ctx.saved_tensors
+        max_q, max_k, is_causal, sm_scale, smooth_k, q_qmax, k_qmax = ctx.cfg
+        if do is None and dlse is None:
+            return None, None, None, None, None, None, None
+        if do is None:
+            do = torch.zeros_like(o)
+        Dg = q.shape[-1]
+        D = 64 if Dg <= 64 else 128
+        qp, kp, vp, op, dop = (_kernel_operand(t, D) for t in (q, k, v, o, do.to(o.dtype)))
+        # written completely by the kernels: tokens outside every sequence get zeros there
+        dq = torch.empty(qp.shape, dtype=q.dtype, device=q.device)
+        dk = torch.empty(kp.shape, dtype=k.dtype, device=k.device)
+        dv = torch.empty(vp.shape, dtype=v.dtype, device=v.device)
+        total_q, Hq, _ = qp.shape
+        total_k, Hkv, _ = kp.shape
+        B = cu_q.shape[0] - 1
+        st = lambda t: _lib.strides2((t.stride(1), t.stride(0)))  # {head, token}
+        if dlse is not None:
+            dlse = dlse.to(torch.float32).contiguous()
+        lib = _lib.load()
+        ws_bytes = lib.lbfa_backward_varlen_workspace_bytes(B, Hq, Hkv, total_q, total_k, max_q, max_k, D, q_qmax,
+                                                            1 if smooth_k else 0)
+        ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=q.device)
+        code = _lib.LBFA_F16 if q.dtype == torch.float16 else _lib.LBFA_BF16
+        with torch.cuda.device(q.device):
+            _lib.check(lib.lbfa_backward_varlen(qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), op.data_ptr(), dop.data_ptr(), code,
+                                                lse.data_ptr(), dlse.data_ptr() if dlse is not None else None,
+                                                dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), cu_q.data_ptr(), cu_k.data_ptr(),
+                                                ws.data_ptr(), ws_bytes, B, Hq, Hkv, total_q, total_k, max_q, max_k, D,
+                                                st(qp), st(kp), st(vp), st(op), st(dop), st(dq), st(dk), st(dv),
+                                                float(sm_scale), int(q_qmax), int(k_qmax), 1 if is_causal else 0,
+                                                1 if smooth_k else 0, torch.cuda.current_stream(q.device).cuda_stream), lib)
+        if D != Dg:
+            dq, dk, dv = dq[..., :Dg], dk[..., :Dg], dv[..., :Dg]
+        return dq, dk, dv, None, None, None, None
+
+
+def varlen_attention(q, k, v, cu_q, cu_k, forward, *, max_seqlen_q, max_seqlen_k, is_causal, sm_scale, smooth_k, q_qmax, k_qmax):
+    """(o, lse [Hq, total_q]) of `forward(q, k, v)` (the packed operator with an LSE) with a backward through
+    `lbfa_backward_varlen`.  cu_q / cu_k: int32 device tensors [B + 1]; no gradient flows to them or to the maxima."""
+    return _VarlenAttentionFn.apply(q, k, v, cu_q, cu_k, forward,
+                                    (int(max_seqlen_q), int(max_seqlen_k), is_causal, float(sm_scale), bool(smooth_k), q_qmax, k_qmax))

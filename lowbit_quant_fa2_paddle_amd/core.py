@@ -203,16 +203,37 @@ def sageattn_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q: int, max_
     cu_seqlens int32 / int64 [B+1] on the device.  As in the reference, smooth-K subtracts ONE mean taken over all
     packed tokens (`k.mean(dim=0)`, :452-454), quantisation blocks restart at every sequence, and each sequence
     attends only to itself (causal: len_q == len_k per sequence).  The whole batch runs in one `lbfa_forward_varlen`
-    call - 4 launches whatever the number of sequences, no host read of cu_seqlens."""
+    call - 4 launches whatever the number of sequences, no host read of cu_seqlens.  Differentiable (torch): with grad
+    mode on and q, k or v requiring grad the call goes through autograd.py (`lbfa_backward_varlen`)."""
+    return _varlen_attention(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, is_causal=is_causal,
+                             sm_scale=sm_scale, smooth_k=smooth_k, q_qmax=127, k_qmax=127, return_lse=False)
+
+
+def _varlen_attention(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, *, is_causal, sm_scale, smooth_k,
+                      q_qmax, k_qmax, return_lse):
+    """The path of `sageattn_varlen`, parameterised on the code range of Q / K; `return_lse` adds the natural-log LSE
+    [Hq, total_q] fp32 (FlashAttention-2's varlen layout, `lbfa_forward_varlen_lse`).  Rows in no sequence are not written."""
     ops, dtype = _check_inputs(q, k, v)
     qshape = ops.shape(q)
     if len(qshape) != 3:
         raise ValueError("sageattn_varlen expects q of shape [total_q, num_qo_heads, head_dim]")
     if 0 in qshape:
-        return ops.empty(qshape, dtype, q)
+        o = ops.empty(qshape, dtype, q)
+        return (o, ops.empty((qshape[1], qshape[0]), ops.float32, q)) if return_lse else o
     if 0 in ops.shape(k):
         raise ValueError("k/v must hold at least one key (softmax over an empty set is undefined)")
     assert ops.shape(cu_seqlens_q) == ops.shape(cu_seqlens_k), "cu_seqlens_q and cu_seqlens_k must have the same length"
+    if _wants_grad(ops, q, k, v):
+        from . import autograd as _ag
+        if sm_scale is None:
+            sm_scale = 1.0 / qshape[-1] ** 0.5
+        cu_q, cu_k = ops.as_int32(cu_seqlens_q), ops.as_int32(cu_seqlens_k)
+        fwd = lambda a, b, c: _varlen_attention(a, b, c, cu_q, cu_k, max_seqlen_q, max_seqlen_k, is_causal=is_causal,
+                                                sm_scale=sm_scale, smooth_k=smooth_k, q_qmax=q_qmax, k_qmax=k_qmax,
+                                                return_lse=True)
+        o, lse = _ag.varlen_attention(q, k, v, cu_q, cu_k, fwd, max_seqlen_q=int(max_seqlen_q), max_seqlen_k=int(max_seqlen_k),
+                                      is_causal=is_causal, sm_scale=sm_scale, smooth_k=smooth_k, q_qmax=q_qmax, k_qmax=k_qmax)
+        return (o, lse) if return_lse else o
     q, k, v, head_dim_og = _pad_head_dim(ops, q, k, v)
     if sm_scale is None:
         sm_scale = 1.0 / head_dim_og ** 0.5  # :455-456
@@ -225,13 +246,18 @@ def sageattn_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q: int, max_
     hs = lambda t: _lib.strides2((ops.strides(t)[1], ops.strides(t)[0]))  # {head, token}
     ws_bytes = lib.lbfa_forward_varlen_workspace_bytes_dt(B, Hq, Hkv, total_q, total_k, int(max_seqlen_q), int(max_seqlen_k), D, ops.dtype_code(q))
     ws = ops.empty((max(ws_bytes, 16),), ops.uint8, q)
+    args = (ops.ptr(cu_q), ops.ptr(cu_k), ops.ptr(ws), ws_bytes, B, Hq, Hkv, total_q, total_k,
+            int(max_seqlen_q), int(max_seqlen_k), D, hs(q), hs(k), hs(v), hs(o),
+            float(sm_scale), int(q_qmax), int(k_qmax), 1 if is_causal else 0, 1 if smooth_k else 0, ops.stream(q))
+    lse = ops.empty((Hq, total_q), ops.float32, q) if return_lse else None
     with ops.device_guard(q):
-        _lib.check(lib.lbfa_forward_varlen(ops.ptr(q), ops.ptr(k), ops.ptr(v), ops.dtype_code(q), ops.ptr(o),
-                                           ops.ptr(cu_q), ops.ptr(cu_k), ops.ptr(ws), ws_bytes, B, Hq, Hkv, total_q, total_k,
-                                           int(max_seqlen_q), int(max_seqlen_k), D, hs(q), hs(k), hs(v), hs(o),
-                                           float(sm_scale), 127, 127, 1 if is_causal else 0, 1 if smooth_k else 0,
-                                           ops.stream(q)), lib)
-    return o[..., :head_dim_og]
+        if return_lse:
+            _lib.check(lib.lbfa_forward_varlen_lse(ops.ptr(q), ops.ptr(k), ops.ptr(v), ops.dtype_code(q), ops.ptr(o), ops.ptr(lse),
+                                                   *args), lib)
+        else:
+            _lib.check(lib.lbfa_forward_varlen(ops.ptr(q), ops.ptr(k), ops.ptr(v), ops.dtype_code(q), ops.ptr(o), *args), lib)
+    o = o[..., :head_dim_og]
+    return (o, lse) if return_lse else o
 
 
 def manual_scaled_dot_product_attention(q, k, v, is_causal=False):

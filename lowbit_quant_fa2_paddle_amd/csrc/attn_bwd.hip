@@ -16,6 +16,12 @@
 //                    and V through LDS); the wave's Q and dO fragments stay in registers.
 // Every sum is formed in one fixed order by one workgroup: results are bitwise reproducible run to run.
 //
+// Packed batches (VARLEN, lbfa_backward_varlen): sequence b owns query tokens [cu_q[b], cu_q[b+1]) and key tokens
+// [cu_k[b], cu_k[b+1]), lengths cut at the maxima Sq / Sk as in the forward; batch strides are 0, rows of lse / dlse / corr
+// / lse2 / delta are [Hq, total_q].  The grids are sized by the maxima and workgroups past a sequence's end exit at once; the
+// same three kernels then run on per-sequence bases and lengths, so one packed sequence forms the dense sums in the dense
+// order.  The pre-pass also zeroes the dq / dk / dv rows of tokens that lie in no sequence or past the cut.
+//
 // MFMA: v_mfma_f32_16x16x32_{f16,bf16}.  Lane l holds A[row l&15][k = 8(l>>4) + j] and B[k = 8(l>>4) + j][col l&15], j = 0..7,
 // and receives C[row 4(l>>4) + i][col l&15], i = 0..3.  An accumulator tile pair (rows 0..15 and 16..31) is used directly as
 // the A operand of a product that sums over those rows by taking the k order j < 4 -> row 4(l>>4) + j, j >= 4 -> row
@@ -103,17 +109,53 @@ __device__ __forceinline__ void load_tile(const void* base, int64_t rs, int r0, 
   }
 }
 
+// packed batch: token t lies in a sequence and within its first `cap` tokens (the last b with cu[b] <= t, by bisection)
+__device__ __forceinline__ bool covered(const int* cu, int B, int cap, int t) {
+  if (t < cu[0]) return false;
+  int lo = 0, hi = B;  // cu[lo] <= t; the answer lies in [lo, hi)
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (cu[mid] <= t) lo = mid;
+    else hi = mid;
+  }
+  return t < cu[lo + 1] && t - cu[lo] < cap;
+}
+
+__device__ __forceinline__ void zero_row(unsigned short* r, int D) {
+  for (int c = 0; c < D; ++c) r[c] = 0;
+}
+
 // ------------------------------------------------------------------------------------------------------------------------
 // delta_i = sum_d dO_id O_id - dLSE_i (fp32, d ascending) and lse2_i = (lse_i - corr_i * sm_scale) * log2(e)
+// VARLEN: rows [Hq, total_q], then one thread per key row [Hkv, total_k]; rows of no sequence get zero gradients here
 // ------------------------------------------------------------------------------------------------------------------------
-template <int DT>
+template <int DT, bool VARLEN>
 __global__ void __launch_bounds__(256) bwd_prep_kernel(BwdParams p) {
   const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t rows = (int64_t)p.B * p.Hq * p.Sq;
+  const int S = VARLEN ? p.total_q : p.Sq;
+  const int64_t rows = (int64_t)(VARLEN ? 1 : p.B) * p.Hq * S;
+  if constexpr (VARLEN) {
+    if (row >= rows) {
+      const int64_t kr = row - rows;
+      if (kr >= (int64_t)p.Hkv * p.total_k) return;
+      const int t = (int)(kr % p.total_k), hk = (int)(kr / p.total_k);
+      if (!covered(p.cu_k, p.B, p.Sk, t)) {
+        zero_row(p.dk + hk * p.dkh + t * p.dks, p.D);
+        zero_row(p.dv + hk * p.dvh + t * p.dvs, p.D);
+      }
+      return;
+    }
+  }
   if (row >= rows) return;
-  const int s = (int)(row % p.Sq);
-  const int64_t bh = row / p.Sq;
+  const int s = (int)(row % S);
+  const int64_t bh = row / S;
   const int h = (int)(bh % p.Hq), b = (int)(bh / p.Hq);
+  if constexpr (VARLEN) {
+    if (!covered(p.cu_q, p.B, p.Sq, s)) {
+      zero_row(p.dq + h * p.dqh + s * p.dqs, p.D);
+      return;
+    }
+  }
   const unsigned short* o = p.o + b * p.ob + h * p.oh + s * p.os;
   const unsigned short* d = p.dout + b * p.db + h * p.dh + s * p.ds;
   float acc = 0.f;
@@ -132,7 +174,7 @@ __global__ void __launch_bounds__(256) bwd_prep_kernel(BwdParams p) {
 // ------------------------------------------------------------------------------------------------------------------------
 // dK, dV: one workgroup per (b, kv head, 64-key block)
 // ------------------------------------------------------------------------------------------------------------------------
-template <int D, int DT, bool QUANT, bool CAUSAL>
+template <int D, int DT, bool QUANT, bool CAUSAL, bool VARLEN>
 __global__ void __launch_bounds__(kThreads) bwd_dkdv_kernel(BwdParams p) {
   constexpr int ST = QUANT ? LBFA_F16 : DT;  // MFMA type of the score product
   constexpr int KS = D / 32;                 // k steps over the head dim
@@ -152,17 +194,26 @@ __global__ void __launch_bounds__(kThreads) bwd_dkdv_kernel(BwdParams p) {
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, c16 = lane & 15;
   const int k0 = kb * kBlk;
   const int key = k0 + 16 * w + c16;  // this lane's key as a score column / operand row
+  int Sq = p.Sq, Sk = p.Sk;
+  int64_t qt0 = 0, kt0 = 0;  // first query / key token of the sequence (packed batch)
+  if constexpr (VARLEN) {
+    qt0 = p.cu_q[b]; kt0 = p.cu_k[b];
+    Sq = min(p.cu_q[b + 1] - (int)qt0, p.Sq);
+    Sk = min(p.cu_k[b + 1] - (int)kt0, p.Sk);
+    if (k0 >= Sk) return;  // whole workgroup, before any barrier
+  }
 
   // K (score operand) and V fragments of the wave's 16 keys: lane holds row `key`, k = 8g + j of each 32-wide step
   u16x8 kf[KS], vf[KS];
   {
-    const void* kbase = QUANT ? (const void*)(p.k8 + b * p.k8b + hk * p.k8h) : (const void*)(p.k + b * p.kb + hk * p.kh);
+    const void* kbase = QUANT ? (const void*)(p.k8 + b * p.k8b + hk * p.k8h + kt0 * p.k8s)
+                              : (const void*)(p.k + b * p.kb + hk * p.kh + kt0 * p.ks);
     const int64_t krs = QUANT ? p.k8s : p.ks;
-    const unsigned short* vbase = p.v + b * p.vb + hk * p.vh;
+    const unsigned short* vbase = p.v + b * p.vb + hk * p.vh + kt0 * p.vs;
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
-      kf[s] = load8<QUANT>(kbase, (int64_t)key * krs + 32 * s + 8 * g, key < p.Sk);
-      vf[s] = load8<false>(vbase, (int64_t)key * p.vs + 32 * s + 8 * g, key < p.Sk);
+      kf[s] = load8<QUANT>(kbase, (int64_t)key * krs + 32 * s + 8 * g, key < Sk);
+      vf[s] = load8<false>(vbase, (int64_t)key * p.vs + 32 * s + 8 * g, key < Sk);
     }
   }
   const float ksc = QUANT ? p.k_scale[((int64_t)b * p.Hkv + hk) * p.nK + kb] : 1.f;
@@ -171,28 +222,29 @@ __global__ void __launch_bounds__(kThreads) bwd_dkdv_kernel(BwdParams p) {
 #pragma unroll
   for (int t = 0; t < NT; ++t) dk[t] = dv[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int nqb = (p.Sq + kBlk - 1) / kBlk;
+  const int nqb = (Sq + kBlk - 1) / kBlk;
   const int qb_first = CAUSAL ? kb : 0;  // causal (Sq == Sk): queries below k0 see none of these keys
   for (int hq = hk * p.group; hq < (hk + 1) * p.group; ++hq) {
-    const void* qsb = QUANT ? (const void*)(p.q8 + b * p.q8b + hq * p.q8h) : (const void*)(p.q + b * p.qb + hq * p.qh);
+    const void* qsb = QUANT ? (const void*)(p.q8 + b * p.q8b + hq * p.q8h + qt0 * p.q8s)
+                            : (const void*)(p.q + b * p.qb + hq * p.qh + qt0 * p.qs);
     const int64_t qsrs = QUANT ? p.q8s : p.qs;
-    const unsigned short* qraw = p.q + b * p.qb + hq * p.qh;
-    const unsigned short* dob = p.dout + b * p.db + hq * p.dh;
-    const int64_t rowbase = ((int64_t)b * p.Hq + hq) * p.Sq;
+    const unsigned short* qraw = p.q + b * p.qb + hq * p.qh + qt0 * p.qs;
+    const unsigned short* dob = p.dout + b * p.db + hq * p.dh + qt0 * p.ds;
+    const int64_t rowbase = VARLEN ? (int64_t)hq * p.total_q + qt0 : ((int64_t)b * p.Hq + hq) * p.Sq;
     for (int qb = qb_first; qb < nqb; ++qb) {
       const int q0 = qb * kBlk;
       __syncthreads();  // the previous tile's readers are done
       if constexpr (QUANT) {
-        load_tile<D, true>(qsb, qsrs, q0, p.Sq, sQ, nullptr);
-        load_tile<D, false>(qraw, p.qs, q0, p.Sq, nullptr, sQT);
+        load_tile<D, true>(qsb, qsrs, q0, Sq, sQ, nullptr);
+        load_tile<D, false>(qraw, p.qs, q0, Sq, nullptr, sQT);
       } else {
-        load_tile<D, false>(qraw, p.qs, q0, p.Sq, sQ, sQT);
+        load_tile<D, false>(qraw, p.qs, q0, Sq, sQ, sQT);
       }
-      load_tile<D, false>(dob, p.ds, q0, p.Sq, sO, sOT);
+      load_tile<D, false>(dob, p.ds, q0, Sq, sO, sOT);
       if (threadIdx.x < kBlk) {
         const int q = q0 + threadIdx.x;
-        sL[threadIdx.x] = q < p.Sq ? p.lse2[rowbase + q] : 0.f;
-        sDelta[threadIdx.x] = q < p.Sq ? p.delta[rowbase + q] : 0.f;
+        sL[threadIdx.x] = q < Sq ? p.lse2[rowbase + q] : 0.f;
+        sDelta[threadIdx.x] = q < Sq ? p.delta[rowbase + q] : 0.f;
       }
       __syncthreads();
       const float sc = QUANT ? p.q_scale[((int64_t)b * p.Hq + hq) * p.nQ + (q0 / LBFA_BLKQ)] * ksc : p.qk_scale;
@@ -214,7 +266,7 @@ __global__ void __launch_bounds__(kThreads) bwd_dkdv_kernel(BwdParams p) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int ql = 16 * t + 4 * g + i, q = q0 + ql;
-          bool ok = q < p.Sq && key < p.Sk;
+          bool ok = q < Sq && key < Sk;
           if (CAUSAL) ok = ok && key <= q;
           const float pv = ok ? __builtin_amdgcn_exp2f(a[i] * sc - sL[ql]) : 0.f;
           a[i] = pv;
@@ -237,12 +289,12 @@ __global__ void __launch_bounds__(kThreads) bwd_dkdv_kernel(BwdParams p) {
     }
   }
   // store: lane holds rows (keys) 16w + 4g + i, column 16t + c16
-  unsigned short* dkb = p.dk + b * p.dkb + hk * p.dkh;
-  unsigned short* dvb = p.dv + b * p.dvb + hk * p.dvh;
+  unsigned short* dkb = p.dk + b * p.dkb + hk * p.dkh + kt0 * p.dks;
+  unsigned short* dvb = p.dv + b * p.dvb + hk * p.dvh + kt0 * p.dvs;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int kr = k0 + 16 * w + 4 * g + i;
-    if (kr >= p.Sk) continue;
+    if (kr >= Sk) continue;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       dkb[(int64_t)kr * p.dks + 16 * t + c16] = store_cvt<DT>(dk[t][i] * p.sm_scale);
@@ -255,7 +307,7 @@ __global__ void __launch_bounds__(kThreads) bwd_dkdv_kernel(BwdParams p) {
 // dQ: one workgroup per (b, q head, 64-row query block).  Scores are formed transposed (S^T = K Q^T: keys on the rows), so
 // dS^T's accumulator tiles are the A operand of dQ = dS K directly.
 // ------------------------------------------------------------------------------------------------------------------------
-template <int D, int DT, bool QUANT, bool CAUSAL>
+template <int D, int DT, bool QUANT, bool CAUSAL, bool VARLEN>
 __global__ void __launch_bounds__(kThreads) bwd_dq_kernel(BwdParams p) {
   constexpr int ST = QUANT ? LBFA_F16 : DT;
   constexpr int KS = D / 32;
@@ -274,20 +326,29 @@ __global__ void __launch_bounds__(kThreads) bwd_dq_kernel(BwdParams p) {
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, c16 = lane & 15;
   const int q0 = qb * kBlk;
   const int q = q0 + 16 * w + c16;  // this lane's query (score column / operand row)
-  const bool qok = q < p.Sq;
+  int Sq = p.Sq, Sk = p.Sk;
+  int64_t qt0 = 0, kt0 = 0;  // first query / key token of the sequence (packed batch)
+  if constexpr (VARLEN) {
+    qt0 = p.cu_q[b]; kt0 = p.cu_k[b];
+    Sq = min(p.cu_q[b + 1] - (int)qt0, p.Sq);
+    Sk = min(p.cu_k[b + 1] - (int)kt0, p.Sk);
+    if (q0 >= Sq) return;  // whole workgroup, before any barrier
+  }
+  const bool qok = q < Sq;
 
   u16x8 qf[KS], of[KS];
   {
-    const void* qsb = QUANT ? (const void*)(p.q8 + b * p.q8b + hq * p.q8h) : (const void*)(p.q + b * p.qb + hq * p.qh);
+    const void* qsb = QUANT ? (const void*)(p.q8 + b * p.q8b + hq * p.q8h + qt0 * p.q8s)
+                            : (const void*)(p.q + b * p.qb + hq * p.qh + qt0 * p.qs);
     const int64_t qsrs = QUANT ? p.q8s : p.qs;
-    const unsigned short* dob = p.dout + b * p.db + hq * p.dh;
+    const unsigned short* dob = p.dout + b * p.db + hq * p.dh + qt0 * p.ds;
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
       qf[s] = load8<QUANT>(qsb, (int64_t)q * qsrs + 32 * s + 8 * g, qok);
       of[s] = load8<false>(dob, (int64_t)q * p.ds + 32 * s + 8 * g, qok);
     }
   }
-  const int64_t row = ((int64_t)b * p.Hq + hq) * p.Sq + q;
+  const int64_t row = (VARLEN ? (int64_t)hq * p.total_q + qt0 : ((int64_t)b * p.Hq + hq) * p.Sq) + q;
   const float l2 = qok ? p.lse2[row] : 0.f, dl = qok ? p.delta[row] : 0.f;
   const float qsc = QUANT ? p.q_scale[((int64_t)b * p.Hq + hq) * p.nQ + (q0 / LBFA_BLKQ)] : p.qk_scale;
 
@@ -295,22 +356,24 @@ __global__ void __launch_bounds__(kThreads) bwd_dq_kernel(BwdParams p) {
 #pragma unroll
   for (int t = 0; t < NT; ++t) dq[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const void* ksb = QUANT ? (const void*)(p.k8 + b * p.k8b + hk * p.k8h) : (const void*)(p.k + b * p.kb + hk * p.kh);
+  const void* ksb = QUANT ? (const void*)(p.k8 + b * p.k8b + hk * p.k8h + kt0 * p.k8s)
+                          : (const void*)(p.k + b * p.kb + hk * p.kh + kt0 * p.ks);
   const int64_t ksrs = QUANT ? p.k8s : p.ks;
-  const unsigned short* kraw = p.k + b * p.kb + hk * p.kh;
-  const unsigned short* vb = p.v + b * p.vb + hk * p.vh;
-  const int nkb = (p.Sk + kBlk - 1) / kBlk;
-  const int kb_end = CAUSAL ? qb + 1 : nkb;  // causal (Sq == Sk): keys beyond q0 + 63 are masked for the whole block
+  const unsigned short* kraw = p.k + b * p.kb + hk * p.kh + kt0 * p.ks;
+  const unsigned short* vb = p.v + b * p.vb + hk * p.vh + kt0 * p.vs;
+  const int nkb = (Sk + kBlk - 1) / kBlk;
+  int kb_end = CAUSAL ? qb + 1 : nkb;  // causal (Sq == Sk): keys beyond q0 + 63 are masked for the whole block
+  if constexpr (VARLEN && CAUSAL) kb_end = min(kb_end, nkb);  // len_q == len_k is the caller's promise: stay in the scale rows
   for (int kb = 0; kb < kb_end; ++kb) {
     const int k0 = kb * kBlk;
     __syncthreads();
     if constexpr (QUANT) {
-      load_tile<D, true>(ksb, ksrs, k0, p.Sk, sK, nullptr);
-      load_tile<D, false>(kraw, p.ks, k0, p.Sk, nullptr, sKT);
+      load_tile<D, true>(ksb, ksrs, k0, Sk, sK, nullptr);
+      load_tile<D, false>(kraw, p.ks, k0, Sk, nullptr, sKT);
     } else {
-      load_tile<D, false>(kraw, p.ks, k0, p.Sk, sK, sKT);
+      load_tile<D, false>(kraw, p.ks, k0, Sk, sK, sKT);
     }
-    load_tile<D, false>(vb, p.vs, k0, p.Sk, sV, nullptr);
+    load_tile<D, false>(vb, p.vs, k0, Sk, sV, nullptr);
     __syncthreads();
     const float sc = QUANT ? qsc * p.k_scale[((int64_t)b * p.Hkv + hk) * p.nK + kb] : qsc;
 
@@ -329,7 +392,7 @@ __global__ void __launch_bounds__(kThreads) bwd_dq_kernel(BwdParams p) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int kk = k0 + 16 * t + 4 * g + i;
-        bool ok = qok && kk < p.Sk;
+        bool ok = qok && kk < Sk;
         if (CAUSAL) ok = ok && kk <= q;
         const float pv = ok ? __builtin_amdgcn_exp2f(a[i] * sc - l2) : 0.f;
         d[i] = pv * (d[i] - dl);
@@ -344,34 +407,37 @@ __global__ void __launch_bounds__(kThreads) bwd_dq_kernel(BwdParams p) {
     }
   }
   // store: lane holds rows (queries) 16w + 4g + i, column 16t + c16
-  unsigned short* dqb = p.dq + b * p.dqb + hq * p.dqh;
+  unsigned short* dqb = p.dq + b * p.dqb + hq * p.dqh + qt0 * p.dqs;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int qr = q0 + 16 * w + 4 * g + i;
-    if (qr >= p.Sq) continue;
+    if (qr >= Sq) continue;
 #pragma unroll
     for (int t = 0; t < NT; ++t) dqb[(int64_t)qr * p.dqs + 16 * t + c16] = store_cvt<DT>(dq[t][i] * p.sm_scale);
   }
 }
 
-template <int D, int DT, bool QUANT, bool CAUSAL>
+template <int D, int DT, bool QUANT, bool CAUSAL, bool VARLEN>
 hipError_t launch_bwd_t(const BwdParams& p, hipStream_t stream) {
-  const unsigned rows = (unsigned)((int64_t)p.B * p.Hq * p.Sq);
-  hipLaunchKernelGGL((bwd_prep_kernel<DT>), dim3((rows + 255) / 256), dim3(256), 0, stream, p);
+  const unsigned rows = VARLEN ? (unsigned)((int64_t)p.Hq * p.total_q + (int64_t)p.Hkv * p.total_k)
+                               : (unsigned)((int64_t)p.B * p.Hq * p.Sq);
+  hipLaunchKernelGGL((bwd_prep_kernel<DT, VARLEN>), dim3((rows + 255) / 256), dim3(256), 0, stream, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   const unsigned nkb = (unsigned)((p.Sk + kBlk - 1) / kBlk), nqb = (unsigned)((p.Sq + kBlk - 1) / kBlk);
-  hipLaunchKernelGGL((bwd_dkdv_kernel<D, DT, QUANT, CAUSAL>), dim3(nkb * p.Hkv * p.B), dim3(kThreads), 0, stream, p);
+  hipLaunchKernelGGL((bwd_dkdv_kernel<D, DT, QUANT, CAUSAL, VARLEN>), dim3(nkb * p.Hkv * p.B), dim3(kThreads), 0, stream, p);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((bwd_dq_kernel<D, DT, QUANT, CAUSAL>), dim3(nqb * p.Hq * p.B), dim3(kThreads), 0, stream, p);
+  hipLaunchKernelGGL((bwd_dq_kernel<D, DT, QUANT, CAUSAL, VARLEN>), dim3(nqb * p.Hq * p.B), dim3(kThreads), 0, stream, p);
   return hipGetLastError();
 }
 
 template <int D, int DT>
 hipError_t launch_bwd_d(const BwdParams& p, bool quant, bool causal, hipStream_t stream) {
-  if (quant) return causal ? launch_bwd_t<D, DT, true, true>(p, stream) : launch_bwd_t<D, DT, true, false>(p, stream);
-  return causal ? launch_bwd_t<D, DT, false, true>(p, stream) : launch_bwd_t<D, DT, false, false>(p, stream);
+  if (p.cu_q != nullptr)  // packed batches are always quantised (the varlen forward has no un-quantised mode)
+    return causal ? launch_bwd_t<D, DT, true, true, true>(p, stream) : launch_bwd_t<D, DT, true, false, true>(p, stream);
+  if (quant) return causal ? launch_bwd_t<D, DT, true, true, false>(p, stream) : launch_bwd_t<D, DT, true, false, false>(p, stream);
+  return causal ? launch_bwd_t<D, DT, false, true, false>(p, stream) : launch_bwd_t<D, DT, false, false, false>(p, stream);
 }
 
 }  // namespace

@@ -129,8 +129,12 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd16_kernel(AttnPa
   int Sq = p.Sq, Sk = p.Sk, nK = p.nK;
   int64_t q_off = (int64_t)b * p.qb, k_off = (int64_t)b * p.kb, v_off = (int64_t)b * p.vb, o_off = (int64_t)b * p.ob;
   int64_t qsc_base = (int64_t)b * p.qsc_b, ksc_base = (int64_t)b * p.ksc_b;
+  int64_t lse_base = ((int64_t)b * p.Hq + h) * p.Sq;  // LSE index of query row 0: [B,Hq,Sq]
+  int vec_b = b;                                       // which q_dot_vec set: one per batch entry
   if (p.cu_q != nullptr) {  // packed variable-length batch (attn_qk_int8_block_varlen.py:125-141); lengths cut at the maxima
     const int q0 = p.cu_q[b], k0 = p.cu_k[b];
+    lse_base = (int64_t)h * p.lse_hs + q0;  // [Hq, total_q]
+    vec_b = 0;                              // one mean over all packed tokens
     Sq = min(p.cu_q[b + 1] - q0, p.Sq);
     Sk = min(p.cu_k[b + 1] - k0, p.Sk);
     if (qt * 128 >= Sq) return;  // whole workgroup, before any barrier
@@ -232,7 +236,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd16_kernel(AttnPa
     // in-kernel Q quantiser: same arithmetic as quant_per_block_kernel (src/triton/quant_per_block.py:132-178)
     float xs[2][KS][16];
     float amax = 0.f;
-    const unsigned short* vec = p.q_dot_vec ? p.q_dot_vec + ((int64_t)b * p.Hkv + hk) * D : nullptr;
+    const unsigned short* vec = p.q_dot_vec ? p.q_dot_vec + ((int64_t)vec_b * p.Hkv + hk) * D : nullptr;
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb) {
       float dot = 0.f;
@@ -763,7 +767,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd16_kernel(AttnPa
       }
       if (p.lse != nullptr && g == 0) {
         float ls = log2f(l_tot[rb]) + m_run[rb];  // base-2 domain (attn_qk_int8_per_block.py:164-167)
-        const int64_t li = ((int64_t)b * p.Hq + h) * p.Sq + qrow;
+        const int64_t li = lse_base + qrow;
         ls *= p.lse_scale;
         if constexpr (QQ) ls += row_corr[rb] * p.lse_corr_scale;
         else if (p.lse_corr != nullptr) ls += p.lse_corr[li] * p.lse_corr_scale;

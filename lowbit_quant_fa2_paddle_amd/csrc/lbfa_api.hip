@@ -53,6 +53,7 @@ void dense_scale_layout(lbfa::AttnParams& p) {
   p.cu_q = p.cu_k = p.cu_qscale = p.cu_kscale = nullptr;
   p.qk_scale = 0.f;
   p.q_sm_scale = 0.f; p.q_qmax = 127.f; p.q_dot_vec = nullptr;
+  p.lse_hs = 0;
 }
 // head dims the one-call operators take directly: the kernels work on 64 / 128 channels and treat the rest as the
 // zero padding of src/core.py:277-287 (never read, never written)
@@ -170,6 +171,7 @@ int quant_impl(const void* x, int dtype, const void* mean, int mean_group, int8_
   p.mean_out = mean_partial ? (unsigned short*)const_cast<void*>(mean) : nullptr;
   p.mean_nsplit = mean_nsplit;
   p.mean_S = S;
+  p.rowdot_hs = 0; p.s_cap = 0x7fffffff;
   g_err[0] = 0;
   return check_hip(lbfa::launch_quant_per_block(p, dtype, D, blk, (hipStream_t)stream), "lbfa_quant_per_block launch");
 }
@@ -188,7 +190,8 @@ namespace {
 int quant_varlen_core(const char* who, const void* x, int dtype, const void* mean, int mean_group, int8_t* out, float* scale,
                       const int32_t* cu_seqlens, const int32_t* cu_scale, float sm_scale, int qmax, int blk, int B,
                       int max_seqlen, int H, int D, int d_valid, const int64_t strides_x[2], const int64_t strides_out[2],
-                      void* stream) {
+                      void* stream, const void* rowdot_vec = nullptr, int rowdot_group = 1, float* rowdot_out = nullptr,
+                      int64_t rowdot_hs = 0, bool cut = false) {
   if (!x || !out || !scale || !cu_seqlens || !strides_x || !strides_out) return fail(LBFA_EINVAL, "%s: null pointer", who);
   if (!dims_ok(B, H, max_seqlen, D)) return fail(LBFA_EINVAL, "Unsupported head_dim: %d (or empty batch %dx%dx%d)", D, B, H, max_seqlen);
   if (dtype != LBFA_F16 && dtype != LBFA_BF16)
@@ -205,8 +208,11 @@ int quant_varlen_core(const char* who, const void* x, int dtype, const void* mea
   p.mean = (const unsigned short*)mean;
   p.out = out;
   p.scale = scale;
-  p.rowdot_vec = nullptr;
-  p.rowdot_out = nullptr;
+  // rowdot_out (if rowdot_vec): [H, rowdot_hs] fp32, row r of sequence b at cu_seqlens[b] + r
+  p.rowdot_vec = (const unsigned short*)rowdot_vec;
+  p.rowdot_out = rowdot_vec ? rowdot_out : nullptr;
+  p.rowdot_hs = rowdot_hs;
+  p.s_cap = cut ? max_seqlen : 0x7fffffff;  // cut: lengths cut at max_seqlen, as the attention kernel cuts them
   p.xb = 0; p.xh = strides_x[0]; p.xs = strides_x[1];
   p.ob = 0; p.oh = strides_out[0]; p.os = strides_out[1];
   p.sm_scale = sm_scale;
@@ -214,7 +220,7 @@ int quant_varlen_core(const char* who, const void* x, int dtype, const void* mea
   p.B = B; p.H = H; p.S = max_seqlen;
   p.nblk = (max_seqlen + blk - 1) / blk;  // grid extent; blocks past a sequence's end exit at once
   p.mean_group = mean ? mean_group : 1;
-  p.rowdot_group = 1;
+  p.rowdot_group = rowdot_vec ? rowdot_group : 1;
   if (cu_scale) { p.scale_b = H; p.scale_h = 1; p.scale_blk = H; }              // [sum_blocks, H]
   else { p.scale_b = (int64_t)H * p.nblk; p.scale_h = p.nblk; p.scale_blk = 1; }  // [B, H, max_blocks]
   p.cu_seqlens = cu_seqlens; p.cu_scale = cu_scale; p.mean_b = 0;
@@ -525,7 +531,8 @@ int attn_varlen_core(const char* who, const int8_t* q, const int8_t* k, const vo
                      const float* q_scale, const float* k_scale, const int32_t* cu_q, const int32_t* cu_k,
                      const int32_t* cu_qscale, const int32_t* cu_kscale, int B, int Hq, int Hkv, int max_q, int max_k, int D,
                      int d_valid, const int64_t sq[2], const int64_t sk[2], const int64_t sv[2], const int64_t so[2], int is_causal,
-                     void* stream, bool quantise_q = false, float q_sm_scale = 0.f, int q_qmax = 127) {
+                     void* stream, bool quantise_q = false, float q_sm_scale = 0.f, int q_qmax = 127, float* lse = nullptr,
+                     int total_q = 0, const void* km = nullptr, double sm_scale = 0.0) {
   if (!q || !k || !v || !o || (!q_scale && !quantise_q) || !k_scale || !cu_q || !cu_k || !sq || !sk || !sv || !so)
     return fail(LBFA_EINVAL, "%s: null pointer", who);
   if ((cu_qscale == nullptr) != (cu_kscale == nullptr)) return fail(LBFA_EINVAL, "%s: give both scale offset tables or neither", who);
@@ -567,6 +574,13 @@ int attn_varlen_core(const char* who, const int8_t* q, const int8_t* k, const vo
   p.cu_q = cu_q; p.cu_k = cu_k; p.cu_qscale = cu_qscale; p.cu_kscale = cu_kscale;
   p.d_valid = d_valid;
   p.q_sm_scale = q_sm_scale; p.q_qmax = (float)q_qmax;
+  if (lse) {  // [Hq, total_q] natural-log LSE with the smooth-K correction formed in the kernel (the q_dot_vec of lbfa_forward)
+    p.lse = lse;
+    p.lse_hs = total_q;
+    p.lse_scale = 1.0f / 1.44269504f;
+    p.lse_corr_scale = (float)sm_scale;
+    p.q_dot_vec = (const unsigned short*)km;
+  }
   if ((int64_t)B * Hq * p.nQ > 0x7fffffffLL) return fail(LBFA_EINVAL, "%s: grid too large", who);
   g_err[0] = 0;
   return check_hip(launch_attention(p, D, v_dtype, o_dtype, is_causal ? 1 : 0, (hipStream_t)stream, quantise_q), who);
@@ -613,7 +627,8 @@ size_t lbfa_forward_varlen_workspace_bytes(int B, int Hq, int Hkv, int total_q, 
   return lbfa_forward_varlen_workspace_bytes_dt(B, Hq, Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, D, LBFA_BF16);  // enough for either dtype
 }
 
-int lbfa_forward_varlen(const void* q, const void* k, const void* v, int dtype, void* o,
+namespace {
+int forward_varlen_impl(const char* who, const void* q, const void* k, const void* v, int dtype, void* o, float* lse,
                         const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, void* workspace, size_t workspace_bytes,
                         int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D,
                         const int64_t strides_q[2], const int64_t strides_k[2], const int64_t strides_v[2],
@@ -621,31 +636,31 @@ int lbfa_forward_varlen(const void* q, const void* k, const void* v, int dtype, 
                         void* stream) {
   const int Dg = D;  // head dim of the caller's tensors
   if (!q || !k || !v || !o || !workspace || !cu_seqlens_q || !cu_seqlens_k || !strides_q || !strides_k || !strides_v || !strides_o)
-    return fail(LBFA_EINVAL, "lbfa_forward_varlen: null pointer");
+    return fail(LBFA_EINVAL, "%s: null pointer", who);
   if (B <= 0 || Hq <= 0 || Hkv <= 0 || total_q <= 0 || total_k <= 0 || max_seqlen_q <= 0 || max_seqlen_k <= 0)
-    return fail(LBFA_EINVAL, "lbfa_forward_varlen: empty batch");
+    return fail(LBFA_EINVAL, "%s: empty batch", who);
   if (!head_dim_ok(Dg)) return fail(LBFA_EINVAL, "Unsupported head_dim: %d", Dg);
   D = padded_head_dim(Dg);
   if (Hq % Hkv != 0) return fail(LBFA_EINVAL, "num_qo_heads (%d) must be divisible by num_kv_heads (%d)", Hq, Hkv);
   const VarlenLayout L = varlen_layout(B, Hq, Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, D, dtype);
-  if (workspace_bytes < L.total) return fail(LBFA_EINVAL, "lbfa_forward_varlen: workspace too small (%zu < %zu)", workspace_bytes, L.total);
-  if (!aligned16(workspace)) return fail(LBFA_EINVAL, "lbfa_forward_varlen: workspace must be 16-byte aligned");
+  if (workspace_bytes < L.total) return fail(LBFA_EINVAL, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, L.total);
+  if (!aligned16(workspace)) return fail(LBFA_EINVAL, "%s: workspace must be 16-byte aligned", who);
   // every argument check before the first launch (see lbfa_forward)
   if (dtype != LBFA_F16 && dtype != LBFA_BF16) return fail(LBFA_EINVAL, "Input tensors must be in dtype of float16 or bfloat16");
-  if (q_qmax != 127 && q_qmax != 7) return fail(LBFA_EINVAL, "lbfa_forward_varlen: q_qmax must be 127 (int8) or 7 (int4 range), got %d", q_qmax);
-  if (k_qmax != 127 && k_qmax != 7) return fail(LBFA_EINVAL, "lbfa_forward_varlen: k_qmax must be 127 (int8) or 7 (int4 range), got %d", k_qmax);
+  if (q_qmax != 127 && q_qmax != 7) return fail(LBFA_EINVAL, "%s: q_qmax must be 127 (int8) or 7 (int4 range), got %d", who, q_qmax);
+  if (k_qmax != 127 && k_qmax != 7) return fail(LBFA_EINVAL, "%s: k_qmax must be 127 (int8) or 7 (int4 range), got %d", who, k_qmax);
   if (!aligned16(q) || !aligned16(k) || !aligned16(v) || (reinterpret_cast<uintptr_t>(o) & 7u))
-    return fail(LBFA_EINVAL, "lbfa_forward_varlen: q/k/v must be 16-byte aligned and o 8-byte aligned");
+    return fail(LBFA_EINVAL, "%s: q/k/v must be 16-byte aligned and o 8-byte aligned", who);
   if ((strides_q[0] | strides_q[1] | strides_k[0] | strides_k[1] | strides_v[0] | strides_v[1]) % 8 != 0)
-    return fail(LBFA_EINVAL, "lbfa_forward_varlen: q / k / v strides must be multiples of 8 elements");
-  if ((strides_o[0] | strides_o[1]) % 4 != 0) return fail(LBFA_EINVAL, "lbfa_forward_varlen: o strides must be multiples of 4 elements");
+    return fail(LBFA_EINVAL, "%s: q / k / v strides must be multiples of 8 elements", who);
+  if ((strides_o[0] | strides_o[1]) % 4 != 0) return fail(LBFA_EINVAL, "%s: o strides must be multiples of 4 elements", who);
   {
     const int64_t lim = 0x7fffffffLL;
     if (2 * (((int64_t)max_seqlen_q + LBFA_BLKQ) * strides_q[1] + D) > lim || ((int64_t)max_seqlen_k + 2 * LBFA_BLKK) * Hkv * D + D > lim ||
         2 * (((int64_t)max_seqlen_k + 2 * LBFA_BLKK) * strides_v[1] + D) > lim)
-      return fail(LBFA_EINVAL, "lbfa_forward_varlen: per-sequence operand window exceeds 2 GiB (token stride x max_seqlen too large)");
+      return fail(LBFA_EINVAL, "%s: per-sequence operand window exceeds 2 GiB (token stride x max_seqlen too large)", who);
   }
-  if ((int64_t)B * Hq * ((max_seqlen_q + LBFA_BLKQ - 1) / LBFA_BLKQ) > 0x7fffffffLL) return fail(LBFA_EINVAL, "lbfa_forward_varlen: grid too large");
+  if ((int64_t)B * Hq * ((max_seqlen_q + LBFA_BLKQ - 1) / LBFA_BLKQ) > 0x7fffffffLL) return fail(LBFA_EINVAL, "%s: grid too large", who);
   char* ws = (char*)workspace;
   void* km = smooth_k ? (void*)(ws + L.km) : nullptr;
   int8_t* k8 = (int8_t*)(ws + L.k8);
@@ -672,9 +687,35 @@ int lbfa_forward_varlen(const void* q, const void* k, const void* v, int dtype, 
     v_dtype = LBFA_F16;
     sv[0] = D; sv[1] = (int64_t)Hkv * D;
   }
-  return attn_varlen_core("lbfa_forward_varlen", (const int8_t*)q, k8, v_in, v_dtype, o, dtype, nullptr, ks, cu_seqlens_q, cu_seqlens_k,
+  // the mean reaches the attention kernel only for the LSE correction: without an LSE this is the call of lbfa_forward_varlen
+  return attn_varlen_core(who, (const int8_t*)q, k8, v_in, v_dtype, o, dtype, nullptr, ks, cu_seqlens_q, cu_seqlens_k,
                           nullptr, nullptr, B, Hq, Hkv, max_seqlen_q, max_seqlen_k, D, Dg, strides_q, sk8, sv, strides_o,
-                          is_causal, stream, true, (float)(sm_scale * 1.44269504), q_qmax);
+                          is_causal, stream, true, (float)(sm_scale * 1.44269504), q_qmax, lse, total_q, lse ? km : nullptr,
+                          sm_scale);
+}
+}  // namespace
+
+int lbfa_forward_varlen(const void* q, const void* k, const void* v, int dtype, void* o,
+                        const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, void* workspace, size_t workspace_bytes,
+                        int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D,
+                        const int64_t strides_q[2], const int64_t strides_k[2], const int64_t strides_v[2],
+                        const int64_t strides_o[2], double sm_scale, int q_qmax, int k_qmax, int is_causal, int smooth_k,
+                        void* stream) {
+  return forward_varlen_impl("lbfa_forward_varlen", q, k, v, dtype, o, nullptr, cu_seqlens_q, cu_seqlens_k, workspace,
+                             workspace_bytes, B, Hq, Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, D, strides_q, strides_k,
+                             strides_v, strides_o, sm_scale, q_qmax, k_qmax, is_causal, smooth_k, stream);
+}
+
+int lbfa_forward_varlen_lse(const void* q, const void* k, const void* v, int dtype, void* o, float* lse,
+                            const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, void* workspace, size_t workspace_bytes,
+                            int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k, int D,
+                            const int64_t strides_q[2], const int64_t strides_k[2], const int64_t strides_v[2],
+                            const int64_t strides_o[2], double sm_scale, int q_qmax, int k_qmax, int is_causal, int smooth_k,
+                            void* stream) {
+  if (reinterpret_cast<uintptr_t>(lse) & 3u) return fail(LBFA_EINVAL, "lbfa_forward_varlen_lse: lse must be 4-byte aligned");
+  return forward_varlen_impl("lbfa_forward_varlen_lse", q, k, v, dtype, o, lse, cu_seqlens_q, cu_seqlens_k, workspace,
+                             workspace_bytes, B, Hq, Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, D, strides_q, strides_k,
+                             strides_v, strides_o, sm_scale, q_qmax, k_qmax, is_causal, smooth_k, stream);
 }
 
 
@@ -797,8 +838,130 @@ int lbfa_backward(const void* q, const void* k, const void* v, const void* o, co
   p.sm_scale = (float)sm_scale;
   p.qk_scale = (float)(sm_scale * 1.44269504);  // as lbfa_sdpa_fwd
   p.corr_scale = (float)sm_scale;               // as lbfa_forward's LSE fix-up
+  p.cu_q = p.cu_k = nullptr;
+  p.total_q = p.total_k = 0;
   g_err[0] = 0;
   return check_hip(lbfa::launch_attn_bwd(p, dtype, quant != 0, is_causal != 0, (hipStream_t)stream), "lbfa_backward launch");
+}
+
+namespace {
+BwdLayout bwd_varlen_layout(int B, int Hq, int Hkv, int total_q, int total_k, int max_q, int max_k, int D, int smooth_k) {
+  BwdLayout L;
+  size_t o = 0;
+  auto take = [&](size_t n) { size_t at = o; o += align256(n); return at; };
+  L.km = take(smooth_k ? (size_t)Hkv * D * 2 : 0);
+  L.part = take(smooth_k ? lbfa_mean_seq_workspace_bytes(1, Hkv, total_k, D) : 0);
+  L.q8 = take((size_t)total_q * Hq * D);
+  L.qs = take((size_t)B * Hq * ((max_q + LBFA_BLKQ - 1) / LBFA_BLKQ) * 4);
+  L.k8 = take((size_t)total_k * Hkv * D);
+  L.ks = take((size_t)B * Hkv * ((max_k + LBFA_BLKK - 1) / LBFA_BLKK) * 4);
+  L.corr = take(smooth_k ? (size_t)Hq * total_q * 4 : 0);
+  L.lse2 = take((size_t)Hq * total_q * 4);
+  L.delta = take((size_t)Hq * total_q * 4);
+  L.total = o;
+  return L;
+}
+bool strides8_2(const int64_t s[2]) { return (s[0] | s[1]) % 8 == 0; }
+}  // namespace
+
+size_t lbfa_backward_varlen_workspace_bytes(int B, int Hq, int Hkv, int total_q, int total_k, int max_seqlen_q, int max_seqlen_k,
+                                            int D, int q_qmax, int smooth_k) {
+  if (B <= 0 || Hq <= 0 || Hkv <= 0 || total_q <= 0 || total_k <= 0 || max_seqlen_q <= 0 || max_seqlen_k <= 0 || (D != 64 && D != 128) ||
+      (q_qmax != 127 && q_qmax != 7))
+    return 0;
+  return bwd_varlen_layout(B, Hq, Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, D, smooth_k).total;
+}
+
+int lbfa_backward_varlen(const void* q, const void* k, const void* v, const void* o, const void* dout, int dtype, const float* lse,
+                         const float* dlse, void* dq, void* dk, void* dv, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k,
+                         void* workspace, size_t workspace_bytes, int B, int Hq, int Hkv, int total_q, int total_k,
+                         int max_seqlen_q, int max_seqlen_k, int D,
+                         const int64_t strides_q[2], const int64_t strides_k[2], const int64_t strides_v[2], const int64_t strides_o[2],
+                         const int64_t strides_dout[2], const int64_t strides_dq[2], const int64_t strides_dk[2],
+                         const int64_t strides_dv[2], double sm_scale, int q_qmax, int k_qmax, int is_causal, int smooth_k,
+                         void* stream) {
+  // every check before the first launch: LBFA_EINVAL means nothing was enqueued
+  if (!q || !k || !v || !o || !dout || !lse || !dq || !dk || !dv || !cu_seqlens_q || !cu_seqlens_k || !workspace || !strides_q ||
+      !strides_k || !strides_v || !strides_o || !strides_dout || !strides_dq || !strides_dk || !strides_dv)
+    return fail(LBFA_EINVAL, "lbfa_backward_varlen: null pointer");
+  if (B <= 0 || Hq <= 0 || Hkv <= 0 || total_q <= 0 || total_k <= 0 || max_seqlen_q <= 0 || max_seqlen_k <= 0)
+    return fail(LBFA_EINVAL, "lbfa_backward_varlen: empty batch");
+  if (D != 64 && D != 128)
+    return fail(LBFA_EINVAL, "lbfa_backward_varlen: Unsupported head_dim: %d (64 or 128; pad other head dims with zeros)", D);
+  if (Hq % Hkv != 0) return fail(LBFA_EINVAL, "num_qo_heads (%d) must be divisible by num_kv_heads (%d)", Hq, Hkv);
+  if (dtype != LBFA_F16 && dtype != LBFA_BF16) return fail(LBFA_EINVAL, "Input tensors must be in dtype of float16 or bfloat16");
+  if ((q_qmax != 7 && q_qmax != 127) || (k_qmax != 7 && k_qmax != 127))
+    return fail(LBFA_EINVAL, "lbfa_backward_varlen: q_qmax / k_qmax must each be 127 or 7, got %d / %d", q_qmax, k_qmax);
+  if (!(sm_scale > 0.0)) return fail(LBFA_EINVAL, "lbfa_backward_varlen: sm_scale must be positive");
+  const void* in16[5] = {q, k, v, o, dout};
+  const int64_t* st16[5] = {strides_q, strides_k, strides_v, strides_o, strides_dout};
+  const char* nm16[5] = {"q", "k", "v", "o", "dout"};
+  for (int i = 0; i < 5; ++i)
+    if (!aligned16(in16[i]) || !strides8_2(st16[i]))
+      return fail(LBFA_EINVAL, "lbfa_backward_varlen: %s must be 16-byte aligned with strides that are multiples of 8 elements", nm16[i]);
+  if ((reinterpret_cast<uintptr_t>(dq) | reinterpret_cast<uintptr_t>(dk) | reinterpret_cast<uintptr_t>(dv)) & 1u)
+    return fail(LBFA_EINVAL, "lbfa_backward_varlen: dq / dk / dv must be 2-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(lse) | reinterpret_cast<uintptr_t>(dlse)) & 3u)
+    return fail(LBFA_EINVAL, "lbfa_backward_varlen: lse / dlse must be 4-byte aligned");
+  const BwdLayout L = bwd_varlen_layout(B, Hq, Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, D, smooth_k);
+  if (workspace_bytes < L.total) return fail(LBFA_EINVAL, "lbfa_backward_varlen: workspace too small (%zu < %zu)", workspace_bytes, L.total);
+  if (!aligned16(workspace)) return fail(LBFA_EINVAL, "lbfa_backward_varlen: workspace must be 16-byte aligned");
+  const int nkb = (max_seqlen_k + 63) / 64, nqb = (max_seqlen_q + 63) / 64;
+  if ((int64_t)Hq * total_q + (int64_t)Hkv * total_k > 0x7fffffffLL - 255 || (int64_t)B * Hq * nqb > 0x7fffffffLL ||
+      (int64_t)B * Hkv * nkb > 0x7fffffffLL)
+    return fail(LBFA_EINVAL, "lbfa_backward_varlen: grid too large");
+
+  // the forward's codes, bit for bit (lbfa_forward_varlen): km over all packed tokens, K by the same quantiser call, Q by the
+  // arithmetic the attention kernel applies in-kernel (128-row blocks restarting at every sequence, lengths cut at
+  // max_seqlen_q, sm_scale * log2(e) folded in) together with the storage-rounded q . km of every packed row
+  char* ws = (char*)workspace;
+  void* km = smooth_k ? (void*)(ws + L.km) : nullptr;
+  int8_t* q8 = (int8_t*)(ws + L.q8);
+  int8_t* k8 = (int8_t*)(ws + L.k8);
+  const int64_t sq8[2] = {D, (int64_t)Hq * D}, sk8[2] = {D, (int64_t)Hkv * D};
+  int st;
+  if (smooth_k) {
+    const int64_t sk3[3] = {0, strides_k[0], strides_k[1]};
+    st = mean_impl(k, dtype, km, ws + L.part, lbfa_mean_seq_workspace_bytes(1, Hkv, total_k, D), 1, Hkv, total_k, D, D, sk3, stream);
+    if (st) return st;
+  }
+  st = quant_varlen_core("lbfa_backward_varlen (K)", k, dtype, km, 1, k8, (float*)(ws + L.ks), cu_seqlens_k, nullptr, 1.0f, k_qmax,
+                         LBFA_BLKK, B, max_seqlen_k, Hkv, D, D, strides_k, sk8, stream);
+  if (st) return st;
+  st = quant_varlen_core("lbfa_backward_varlen (Q)", q, dtype, nullptr, 1, q8, (float*)(ws + L.qs), cu_seqlens_q, nullptr,
+                         (float)(sm_scale * 1.44269504), q_qmax, LBFA_BLKQ, B, max_seqlen_q, Hq, D, D, strides_q, sq8, stream,
+                         km, Hq / Hkv, smooth_k ? (float*)(ws + L.corr) : nullptr, total_q, true);
+  if (st) return st;
+  lbfa::BwdParams p;
+  p.q8 = q8; p.k8 = k8;
+  p.q_scale = (const float*)(ws + L.qs); p.k_scale = (const float*)(ws + L.ks);
+  p.corr = smooth_k ? (const float*)(ws + L.corr) : nullptr;
+  p.q8b = 0; p.q8h = sq8[0]; p.q8s = sq8[1];
+  p.k8b = 0; p.k8h = sk8[0]; p.k8s = sk8[1];
+  p.q = (const unsigned short*)q; p.k = (const unsigned short*)k; p.v = (const unsigned short*)v;
+  p.o = (const unsigned short*)o; p.dout = (const unsigned short*)dout;
+  p.dq = (unsigned short*)dq; p.dk = (unsigned short*)dk; p.dv = (unsigned short*)dv;
+  p.lse = lse; p.dlse = dlse;
+  p.lse2 = (float*)(ws + L.lse2); p.delta = (float*)(ws + L.delta);
+  p.qb = 0; p.qh = strides_q[0]; p.qs = strides_q[1];
+  p.kb = 0; p.kh = strides_k[0]; p.ks = strides_k[1];
+  p.vb = 0; p.vh = strides_v[0]; p.vs = strides_v[1];
+  p.ob = 0; p.oh = strides_o[0]; p.os = strides_o[1];
+  p.db = 0; p.dh = strides_dout[0]; p.ds = strides_dout[1];
+  p.dqb = 0; p.dqh = strides_dq[0]; p.dqs = strides_dq[1];
+  p.dkb = 0; p.dkh = strides_dk[0]; p.dks = strides_dk[1];
+  p.dvb = 0; p.dvh = strides_dv[0]; p.dvs = strides_dv[1];
+  p.B = B; p.Hq = Hq; p.Hkv = Hkv; p.Sq = max_seqlen_q; p.Sk = max_seqlen_k; p.D = D;
+  p.nQ = (max_seqlen_q + LBFA_BLKQ - 1) / LBFA_BLKQ;
+  p.nK = (max_seqlen_k + LBFA_BLKK - 1) / LBFA_BLKK;
+  p.group = Hq / Hkv;
+  p.sm_scale = (float)sm_scale;
+  p.qk_scale = (float)(sm_scale * 1.44269504);
+  p.corr_scale = (float)sm_scale;
+  p.cu_q = cu_seqlens_q; p.cu_k = cu_seqlens_k;
+  p.total_q = total_q; p.total_k = total_k;
+  g_err[0] = 0;
+  return check_hip(lbfa::launch_attn_bwd(p, dtype, true, is_causal != 0, (hipStream_t)stream), "lbfa_backward_varlen launch");
 }
 
 }  // extern "C"

@@ -112,6 +112,10 @@ struct QuantParams {
   const double* mean_partial;  // null: read `mean`
   unsigned short* mean_out;    // may be null
   int mean_nsplit, mean_S;
+  // packed batch only: rowdot_out is [H, total] with head stride rowdot_hs (row r of sequence b at cu_seqlens[b] + r), and
+  // sequence lengths are cut at s_cap (the attention kernel's in-kernel Q quantiser cuts at max_seqlen_q; INT_MAX: uncut)
+  int64_t rowdot_hs;
+  int s_cap;
 };
 
 struct AttnParams {
@@ -143,6 +147,9 @@ struct AttnParams {
   // and the LSE correction q . km comes from the same registers (q_dot_vec = km [B,Hkv,D] or null).
   float q_sm_scale, q_qmax;
   const unsigned short* q_dot_vec;
+  // packed batch with an LSE: lse is [Hq, total_q] (FA2's varlen softmax_lse), lse_hs = total_q; q_dot_vec is then ONE
+  // [Hkv, D] set shared by all sequences.  Unused by the dense path ([B,Hq,Sq]).
+  int64_t lse_hs;
 };
 
 // attention backward (attn_bwd.hip); strides in elements {batch, head, seq}, last dim contiguous, D in {64, 128}
@@ -161,6 +168,10 @@ struct BwdParams {
   float sm_scale;    // natural-log softmax scale: dQ = sm_scale dS K, dK = sm_scale dS^T Q
   float qk_scale;    // un-quantised scores: sm_scale * log2(e)
   float corr_scale;  // sm_scale (multiplies corr)
+  // packed batch (lbfa_backward_varlen) when cu_q != null: strides {0, head, token}, Sq / Sk the maxima, lse / dlse / corr /
+  // lse2 / delta [Hq, total_q], q8 / k8 [total, H, D], scales [B, H, max_blocks]
+  const int *cu_q, *cu_k;
+  int total_q, total_k;
 };
 
 }  // namespace lbfa

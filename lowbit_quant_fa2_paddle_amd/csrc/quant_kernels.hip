@@ -118,10 +118,12 @@ __global__ __launch_bounds__(256) void quant_per_block_kernel(QuantParams p) {
   const int t = threadIdx.x, c = t % CPR, rl = t / CPR;
   int S = p.S;
   int64_t xoff = (int64_t)b * p.xb, ooff = (int64_t)b * p.ob, sbase = (int64_t)b * p.scale_b;
+  [[maybe_unused]] int64_t rdoff = 0;  // rowdot_out index of row 0 (packed batch)
   if (p.cu_seqlens != nullptr) {  // packed batch: sequence b (quant_per_block_varlen.py:41-48)
     const int s0 = p.cu_seqlens[b];
-    S = p.cu_seqlens[b + 1] - s0;
+    S = min(p.cu_seqlens[b + 1] - s0, p.s_cap);
     if (blk0 * BLK >= S) return;
+    if constexpr (HAS_DOT) rdoff = (int64_t)h * p.rowdot_hs + s0;
     xoff = (int64_t)s0 * p.xs;
     ooff = (int64_t)s0 * p.os;
     if (p.cu_scale != nullptr) sbase = (int64_t)p.cu_scale[b] * p.scale_b;
@@ -188,7 +190,8 @@ __global__ __launch_bounds__(256) void quant_per_block_kernel(QuantParams p) {
         for (int i = 0; i < 8; ++i) dot += v[i] * vec[i];
 #pragma unroll
         for (int o = CPR / 2; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
-        if (c == 0 && row < S) p.rowdot_out[((int64_t)b * p.H + h) * S + row] = load_cvt<DT>(store_cvt<DT>(dot));
+        if (c == 0 && row < S)
+          p.rowdot_out[(p.cu_seqlens != nullptr ? rdoff : ((int64_t)b * p.H + h) * S) + row] = load_cvt<DT>(store_cvt<DT>(dot));
       }
 #pragma unroll
       for (int i = 0; i < 8; ++i) {

@@ -1,0 +1,111 @@
+"""CPU float64 restatement of the packed-batch backward contract (include/lowbit_fa.h `lbfa_backward_varlen`): the dense
+contract of bwd_reference.py applied sequence by sequence.
+
+Sequence b owns query tokens [cu_q[b], cu_q[b+1]) and key tokens [cu_k[b], cu_k[b+1]); no gradient crosses a boundary.  The
+forward's km (ONE mean over all packed keys), codes and scales come from `oracle.lowbit_fa_varlen(..., return_intermediates=True)`
+(quantisation blocks restart at every sequence).  Per sequence:
+    lse  = lse2 / log2(e) + dtype(q . km) * sm_scale   (lse2 of oracle.attn_fwd_int8_fp16; -inf for a sequence without keys)
+    P    = exp2(s2 - (lse - dtype(q . km) * sm_scale) * log2(e)),  s2 = codes x scales
+and the gradients of bwd_reference.grads_from_p.  Arrays are packed [total, H, D] (fp32 values already rounded to the storage
+dtype); lse / dlse are [Hq, total_q].  Tokens in no sequence get zero gradients.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from bwd_reference import LOG2E, _mask, grads_from_p
+from oracle import lowbit_fa_oracle as orc
+
+
+def _seq(x, c, b):
+    """[1, H, len, D] panel of sequence b of a packed [total, H, D] array"""
+    return np.transpose(x[c[b]:c[b + 1]], (1, 0, 2))[None]
+
+
+def intermediates(q, k, v, cu_q, cu_k, *, dtype="fp16", is_causal=False, sm_scale=None, smooth_k=True, q_qmax=127, k_qmax=127):
+    """per sequence (None for an empty query range): dict(qi, qs, ki, ks, corr) - the forward's codes [1, H, len, D], scales
+    [1, H, blocks] and the storage-rounded q . km [1, Hq, len_q] (zeros without smooth-K) - and sm_scale"""
+    D = q.shape[-1]
+    sm_scale = 1.0 / D ** 0.5 if sm_scale is None else sm_scale
+    _, it = orc.lowbit_fa_varlen(q, k, v, cu_q, cu_k, dtype=dtype, is_causal=is_causal, sm_scale=sm_scale, smooth_k=smooth_k,
+                                 q_qmax=float(q_qmax), k_qmax=float(k_qmax), tail="neg_inf", amax_floor=1e-7,
+                                 return_intermediates=True)
+    cq, ck = [int(x) for x in cu_q], [int(x) for x in cu_k]
+    g = q.shape[1] // k.shape[1]
+    seqs, qb0, kb0 = [], 0, 0
+    for b in range(len(cq) - 1):
+        lq, lk = cq[b + 1] - cq[b], ck[b + 1] - ck[b]
+        if lq == 0:
+            seqs.append(None)
+            continue
+        nq, nk = -(-lq // 128), (-(-lk // 64) if lk else 0)
+        s = dict(qi=_seq(it["q_i8"], cq, b), ki=_seq(it["k_i8"], ck, b),
+                 qs=np.transpose(it["q_scale"][qb0:qb0 + nq], (1, 0))[None],
+                 ks=np.transpose(it["k_scale"][kb0:kb0 + nk], (1, 0))[None])
+        qb0, kb0 = qb0 + nq, kb0 + nk
+        qf = _seq(q, cq, b).astype(np.float32)
+        if smooth_k:
+            km = np.repeat(np.transpose(it["km"][..., :D], (1, 0, 2))[None], g, axis=1).astype(np.float32)  # [1, Hq, 1, D]
+            s["corr"] = orc.to_storage(np.einsum("bhsd,bhtd->bhs", qf, km), dtype).astype(np.float64)
+        else:
+            s["corr"] = np.zeros(qf.shape[:3])
+        seqs.append(s)
+    return seqs, sm_scale
+
+
+def varlen_lse(q, k, v, cu_q, cu_k, return_corr=False, **kw):
+    """natural-log LSE [Hq, total_q] float64 of the packed forward; rows in no sequence NaN, key-less sequences -inf.
+    return_corr: also the correction term dtype(q . km) * sm_scale of every row (0 in rows of no sequence)"""
+    seqs, sm_scale = intermediates(q, k, v, cu_q, cu_k, **kw)
+    cq, ck = [int(x) for x in cu_q], [int(x) for x in cu_k]
+    out = np.full((q.shape[1], q.shape[0]), np.nan)
+    corr = np.zeros(out.shape)
+    for b, s in enumerate(seqs):
+        if s is None:
+            continue
+        corr[:, cq[b]:cq[b + 1]] = s["corr"][0] * sm_scale
+        if ck[b + 1] == ck[b]:
+            out[:, cq[b]:cq[b + 1]] = -np.inf
+            continue
+        vb = _seq(orc._pad_head_dim(v), ck, b).astype(np.float16).astype(np.float32)  # the codes' padded head dim
+        _, lse2 = orc.attn_fwd_int8_fp16(s["qi"], s["ki"], vb, s["qs"], s["ks"], causal=kw.get("is_causal", False),
+                                         return_lse=True, tail="neg_inf")
+        out[:, cq[b]:cq[b + 1]] = (lse2[0].astype(np.float64) / LOG2E + s["corr"][0] * sm_scale)
+    return (out, corr) if return_corr else out
+
+
+def p_quantised(s, lse, sm_scale, is_causal):
+    """P [1, Hq, len_q, len_k] of one sequence from its codes, scales and the operator's LSE rows [Hq, len_q]"""
+    g = s["qi"].shape[1] // s["ki"].shape[1]
+    Sq, Sk = s["qi"].shape[2], s["ki"].shape[2]
+    si = np.einsum("bhsd,bhtd->bhst", s["qi"].astype(np.float64), np.repeat(s["ki"].astype(np.float64), g, axis=1), optimize=True)
+    qsr = np.repeat(s["qs"].astype(np.float64), 128, axis=2)[:, :, :Sq]
+    ksr = np.repeat(np.repeat(s["ks"].astype(np.float64), 64, axis=2)[:, :, :Sk], g, axis=1)
+    s2 = si * qsr[..., :, None] * ksr[..., None, :]
+    lse2 = (lse[None].astype(np.float64) - s["corr"] * sm_scale) * LOG2E
+    p = np.exp2(s2 - lse2[..., None])
+    return np.where(_mask(Sq, Sk, is_causal), p, 0.0)
+
+
+def varlen_backward(q, k, v, o, lse, do, cu_q, cu_k, *, dtype="fp16", is_causal=False, sm_scale=None, smooth_k=True,
+                    q_qmax=127, k_qmax=127, dlse=None, p_fn=None, only=None):
+    """(dq, dk, dv) float64, packed like q / k / v.  `p_fn(b, q_b, k_b, lse_b, sm_scale)` replaces the quantised P of sequence b
+    (q_b / k_b [1, H, len, D]); `only`: the sequences to compute (others stay zero)."""
+    cq, ck = [int(x) for x in cu_q], [int(x) for x in cu_k]
+    if p_fn is None:
+        seqs, sm_scale = intermediates(q, k, v, cu_q, cu_k, dtype=dtype, is_causal=is_causal, sm_scale=sm_scale,
+                                       smooth_k=smooth_k, q_qmax=q_qmax, k_qmax=k_qmax)
+    else:
+        seqs, sm_scale = None, (1.0 / q.shape[-1] ** 0.5 if sm_scale is None else sm_scale)
+    dq, dk, dv = (np.zeros(x.shape) for x in (q, k, v))
+    for b in range(len(cq) - 1):
+        if (only is not None and b not in only) or cq[b + 1] == cq[b] or ck[b + 1] == ck[b]:
+            continue  # no queries or no keys: every gradient of the sequence is zero
+        qb, kb, vb, ob, dob = (_seq(x, c, b) for x, c in ((q, cq), (k, ck), (v, ck), (o, cq), (do, cq)))
+        lb = lse[:, cq[b]:cq[b + 1]]
+        p = p_quantised(seqs[b], lb, sm_scale, is_causal) if p_fn is None else p_fn(b, qb, kb, lb, sm_scale)
+        dlb = None if dlse is None else dlse[:, cq[b]:cq[b + 1]][None]
+        g = grads_from_p(p, qb, kb, vb, ob, dob, sm_scale=sm_scale, dlse=dlb)
+        for out, gb, c in zip((dq, dk, dv), g, (cq, ck, ck)):
+            out[c[b]:c[b + 1]] = np.transpose(gb[0], (1, 0, 2))
+    return dq, dk, dv
