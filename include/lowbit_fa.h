@@ -222,6 +222,14 @@ int lbfa_sdpa_fwd(const void* q, const void* k, const void* v, int dtype, void* 
  *          scores of lbfa_sdpa_fwd (smooth_k is then ignored).
  *   workspace: >= lbfa_backward_workspace_bytes(B, Hq, Hkv, Sq, Sk, D, q_qmax, smooth_k) bytes, 16-byte aligned; contents
  *          undefined afterwards.  Every argument is checked before the first launch (LBFA_EINVAL: nothing enqueued).
+ *   range: the exponent argument fl(fl(s2 sc) - lse2) and lse2 itself are fp32 values the size of the scores, so P carries a
+ *          relative error of about 5 * 2^-24 * max(|s2|, |lse2|) (s2 = q.k * sm_scale * log2(e), in binades) besides its one
+ *          rounding to the dtype: the gradient error stays at the dtype's rounding of P and dS up to |s2| ~ 2^11 (fp16) /
+ *          2^14 (bf16) and grows linearly beyond (about 2^-8 relative in P at the 2^14..2^15 of randint(-100, 100) inputs
+ *          at D = 128, whose saturated softmax leaves gradients at the fp32 residue of dP - delta).  The smooth-K
+ *          correction taken out of the LSE is the forward's own, bit for bit: the pre-pass forms dtype(q . km) in the
+ *          forward kernels' fp32 order (one dtype ulp of it would move a whole row of P by ulp * sm_scale * log2(e)).
+ *          Per-element bound: tests/bwd_reference.py `grad_bound`.
  */
 size_t lbfa_backward_workspace_bytes(int B, int Hq, int Hkv, int Sq, int Sk, int D, int q_qmax, int smooth_k);
 int lbfa_backward(const void* q, const void* k, const void* v, const void* o, const void* dout, int dtype, const float* lse,

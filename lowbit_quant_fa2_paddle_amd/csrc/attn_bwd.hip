@@ -128,6 +128,27 @@ __device__ __forceinline__ void zero_row(unsigned short* r, int D) {
 // ------------------------------------------------------------------------------------------------------------------------
 // delta_i = sum_d dO_id O_id - dLSE_i (fp32, d ascending) and lse2_i = (lse_i - corr_i * sm_scale) * log2(e)
 // VARLEN: rows [Hq, total_q], then one thread per key row [Hkv, total_k]; rows of no sequence get zero gradients here
+// corr_i = dtype(q_i . km) is the value the forward added to the LSE, formed in the forward kernels' order (the in-kernel Q
+// quantiser of attn_fwd16.hip / attn_fwd.hip): lane group g = 0..3 of a row sums the exact products of columns
+// 64 s + 16 g + 0..15, s ascending, in sequence; then (S0 + S1) + (S2 + S3), rounded to the dtype.  Any other order can round
+// to the neighbouring dtype value, which scales every P of the row by 2^(ulp(corr) * sm_scale * log2(e)).
+template <int DT>
+__device__ __forceinline__ float fwd_corr(const unsigned short* q, const unsigned short* km, int D) {
+  float part[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int s = 0; s < D; s += 64) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+        const int c = s + 16 * g + 8 * hf;
+        const u16x8 qv = *reinterpret_cast<const u16x8*>(q + c), kv = *reinterpret_cast<const u16x8*>(km + c);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) part[g] = part[g] + load_cvt<DT>(qv[e]) * load_cvt<DT>(kv[e]);
+      }
+  }
+  return load_cvt<DT>(store_cvt<DT>((part[0] + part[1]) + (part[2] + part[3])));
+}
+
 // ------------------------------------------------------------------------------------------------------------------------
 template <int DT, bool VARLEN>
 __global__ void __launch_bounds__(256) bwd_prep_kernel(BwdParams p) {
@@ -167,7 +188,7 @@ __global__ void __launch_bounds__(256) bwd_prep_kernel(BwdParams p) {
   if (p.dlse) acc -= p.dlse[row];
   p.delta[row] = acc;
   float l = p.lse[row];
-  if (p.corr) l -= p.corr[row] * p.corr_scale;
+  if (p.km) l -= fwd_corr<DT>(p.q + b * p.qb + h * p.qh + s * p.qs, p.km + ((int64_t)b * p.Hkv + h / p.group) * p.D, p.D) * p.corr_scale;
   p.lse2[row] = l * kLog2e;
 }
 

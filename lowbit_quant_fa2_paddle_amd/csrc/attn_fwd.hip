@@ -187,7 +187,9 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(AttnPara
     const char* qsrc = (const char*)p.q + 2 * (q_off + (int64_t)h * p.qh);
     const __amdgpu_buffer_rsrc_t q_rs = make_rsrc(qsrc, (unsigned)(2 * ((int64_t)(Sq - 1) * p.qs + p.d_valid)));
     float xs[KS][16];
-    float amax = 0.f, dot = 0.f;
+    // q . km in attn_fwd16.hip's order (one value of the correction for every operator and for the backward's pre-pass):
+    // this lane's 16 columns of step s are those of lane group g = 2 (s & 1) + hh of a 64-column step there
+    float amax = 0.f, dot[2] = {0.f, 0.f};
     const unsigned short* vec = p.q_dot_vec ? p.q_dot_vec + ((int64_t)b * p.Hkv + hk) * D : nullptr;
 #pragma unroll
     for (int s = 0; s < KS; ++s)
@@ -207,10 +209,11 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(AttnPara
           const u32x4 vraw = *reinterpret_cast<const u32x4*>(vec + col);
 #pragma unroll
           for (int e = 0; e < 8; ++e)
-            dot += xv[e] * load_cvt<OT>((unsigned short)((e & 1) ? (vraw[e >> 1] >> 16) : (vraw[e >> 1] & 0xffffu)));
+            dot[s & 1] += xv[e] * load_cvt<OT>((unsigned short)((e & 1) ? (vraw[e >> 1] >> 16) : (vraw[e >> 1] & 0xffffu)));
         }
       }
-    row_corr = load_cvt<OT>(store_cvt<OT>(half_swap_sum(dot)));  // rounded to the storage dtype (src/core.py:294-304)
+    // (S0 + S1) + (S2 + S3), rounded to the storage dtype (src/core.py:294-304)
+    row_corr = load_cvt<OT>(store_cvt<OT>(half_swap_sum(dot[0]) + half_swap_sum(dot[1])));
     amax = wave_max_nonneg(amax);
     float* red = reinterpret_cast<float*>(smem + TILES_BYTES);
     if (lane == 0) red[wave] = amax;

@@ -724,7 +724,7 @@ int lbfa_forward_varlen_lse(const void* q, const void* k, const void* v, int dty
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 struct BwdLayout {
-  size_t km, part, q8, qs, k8, ks, corr, lse2, delta, total;
+  size_t km, part, q8, qs, k8, ks, lse2, delta, total;
 };
 BwdLayout bwd_layout(int B, int Hq, int Hkv, int Sq, int Sk, int D, int quant, int smooth_k) {
   BwdLayout L;
@@ -737,7 +737,6 @@ BwdLayout bwd_layout(int B, int Hq, int Hkv, int Sq, int Sk, int D, int quant, i
   L.qs = take(quant ? (size_t)B * Hq * ((Sq + LBFA_BLKQ - 1) / LBFA_BLKQ) * 4 : 0);
   L.k8 = take(quant ? (size_t)B * Hkv * Sk * D : 0);
   L.ks = take(quant ? (size_t)B * Hkv * ((Sk + LBFA_BLKK - 1) / LBFA_BLKK) * 4 : 0);
-  L.corr = take(sm ? (size_t)B * Hq * Sq * 4 : 0);
   L.lse2 = take((size_t)B * Hq * Sq * 4);
   L.delta = take((size_t)B * Hq * Sq * 4);
   L.total = o;
@@ -792,7 +791,7 @@ int lbfa_backward(const void* q, const void* k, const void* v, const void* o, co
   lbfa::BwdParams p;
   p.q8 = p.k8 = nullptr;
   p.q_scale = p.k_scale = nullptr;
-  p.corr = nullptr;
+  p.km = nullptr;
   p.q8b = p.q8h = p.q8s = p.k8b = p.k8h = p.k8s = 0;
   int st;
   if (quant) {
@@ -809,12 +808,13 @@ int lbfa_backward(const void* q, const void* k, const void* v, const void* o, co
     st = quant_impl(k, dtype, km, 1, k8, (float*)(ws + L.ks), 1.0f, k_qmax, LBFA_BLKK, B, Hkv, Sk, D, D, strides_k, sk8, nullptr, 1,
                     nullptr, stream);
     if (st) return st;
+    // the smooth-K correction q . km is formed by the pre-pass in the forward kernels' order (bwd_prep_kernel), not here
     st = quant_impl(q, dtype, nullptr, 1, q8, (float*)(ws + L.qs), (float)(sm_scale * 1.44269504), q_qmax, LBFA_BLKQ, B, Hq, Sq, D, D,
-                    strides_q, sq8, km, Hq / Hkv, sm ? (float*)(ws + L.corr) : nullptr, stream);
+                    strides_q, sq8, nullptr, 1, nullptr, stream);
     if (st) return st;
     p.q8 = q8; p.k8 = k8;
     p.q_scale = (const float*)(ws + L.qs); p.k_scale = (const float*)(ws + L.ks);
-    p.corr = sm ? (const float*)(ws + L.corr) : nullptr;
+    p.km = (const unsigned short*)km;
     p.q8b = sq8[0]; p.q8h = sq8[1]; p.q8s = sq8[2];
     p.k8b = sk8[0]; p.k8h = sk8[1]; p.k8s = sk8[2];
   }
@@ -855,7 +855,6 @@ BwdLayout bwd_varlen_layout(int B, int Hq, int Hkv, int total_q, int total_k, in
   L.qs = take((size_t)B * Hq * ((max_q + LBFA_BLKQ - 1) / LBFA_BLKQ) * 4);
   L.k8 = take((size_t)total_k * Hkv * D);
   L.ks = take((size_t)B * Hkv * ((max_k + LBFA_BLKK - 1) / LBFA_BLKK) * 4);
-  L.corr = take(smooth_k ? (size_t)Hq * total_q * 4 : 0);
   L.lse2 = take((size_t)Hq * total_q * 4);
   L.delta = take((size_t)Hq * total_q * 4);
   L.total = o;
@@ -913,7 +912,8 @@ int lbfa_backward_varlen(const void* q, const void* k, const void* v, const void
 
   // the forward's codes, bit for bit (lbfa_forward_varlen): km over all packed tokens, K by the same quantiser call, Q by the
   // arithmetic the attention kernel applies in-kernel (128-row blocks restarting at every sequence, lengths cut at
-  // max_seqlen_q, sm_scale * log2(e) folded in) together with the storage-rounded q . km of every packed row
+  // max_seqlen_q, sm_scale * log2(e) folded in); the storage-rounded q . km of every packed row is formed by the pre-pass in
+  // the attention kernel's order (bwd_prep_kernel)
   char* ws = (char*)workspace;
   void* km = smooth_k ? (void*)(ws + L.km) : nullptr;
   int8_t* q8 = (int8_t*)(ws + L.q8);
@@ -930,12 +930,12 @@ int lbfa_backward_varlen(const void* q, const void* k, const void* v, const void
   if (st) return st;
   st = quant_varlen_core("lbfa_backward_varlen (Q)", q, dtype, nullptr, 1, q8, (float*)(ws + L.qs), cu_seqlens_q, nullptr,
                          (float)(sm_scale * 1.44269504), q_qmax, LBFA_BLKQ, B, max_seqlen_q, Hq, D, D, strides_q, sq8, stream,
-                         km, Hq / Hkv, smooth_k ? (float*)(ws + L.corr) : nullptr, total_q, true);
+                         nullptr, 1, nullptr, 0, true);
   if (st) return st;
   lbfa::BwdParams p;
   p.q8 = q8; p.k8 = k8;
   p.q_scale = (const float*)(ws + L.qs); p.k_scale = (const float*)(ws + L.ks);
-  p.corr = smooth_k ? (const float*)(ws + L.corr) : nullptr;
+  p.km = (const unsigned short*)km;
   p.q8b = 0; p.q8h = sq8[0]; p.q8s = sq8[1];
   p.k8b = 0; p.k8h = sk8[0]; p.k8s = sk8[1];
   p.q = (const unsigned short*)q; p.k = (const unsigned short*)k; p.v = (const unsigned short*)v;

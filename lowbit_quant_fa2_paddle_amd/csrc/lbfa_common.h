@@ -160,15 +160,15 @@ struct BwdParams {
   const float *q_scale, *k_scale;              // [B,Hq,nQ] / [B,Hkv,nK] contiguous
   const float* lse;    // [B,Hq,Sq] natural-log LSE as the forward returned it
   const float* dlse;   // [B,Hq,Sq] or null
-  const float* corr;   // smooth-K correction q . km [B,Hq,Sq] (storage-dtype rounded) or null
+  const unsigned short* km;  // smooth-K mean in the dtype, [B,Hkv,D] (packed batch: [Hkv,D]), or null
   float *lse2, *delta; // [B,Hq,Sq] workspace: base-2 LSE without the correction, rowsum(dO o O) - dLSE
   int64_t qb, qh, qs, kb, kh, ks, vb, vh, vs, ob, oh, os, db, dh, ds;
   int64_t dqb, dqh, dqs, dkb, dkh, dks, dvb, dvh, dvs, q8b, q8h, q8s, k8b, k8h, k8s;
   int B, Hq, Hkv, Sq, Sk, D, nQ, nK, group;
   float sm_scale;    // natural-log softmax scale: dQ = sm_scale dS K, dK = sm_scale dS^T Q
   float qk_scale;    // un-quantised scores: sm_scale * log2(e)
-  float corr_scale;  // sm_scale (multiplies corr)
-  // packed batch (lbfa_backward_varlen) when cu_q != null: strides {0, head, token}, Sq / Sk the maxima, lse / dlse / corr /
+  float corr_scale;  // sm_scale (multiplies the correction q . km)
+  // packed batch (lbfa_backward_varlen) when cu_q != null: strides {0, head, token}, Sq / Sk the maxima, lse / dlse /
   // lse2 / delta [Hq, total_q], q8 / k8 [total, H, D], scales [B, H, max_blocks]
   const int *cu_q, *cu_k;
   int total_q, total_k;

@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from bwd_reference import LOG2E, _mask, grads_from_p
+from bwd_reference import LOG2E, _mask, fwd_corr, grad_bound, grads_from_p, quantised_arg_err
 from oracle import lowbit_fa_oracle as orc
 
 
@@ -46,7 +46,7 @@ def intermediates(q, k, v, cu_q, cu_k, *, dtype="fp16", is_causal=False, sm_scal
         qf = _seq(q, cq, b).astype(np.float32)
         if smooth_k:
             km = np.repeat(np.transpose(it["km"][..., :D], (1, 0, 2))[None], g, axis=1).astype(np.float32)  # [1, Hq, 1, D]
-            s["corr"] = orc.to_storage(np.einsum("bhsd,bhtd->bhs", qf, km), dtype).astype(np.float64)
+            s["corr"] = fwd_corr(qf, km, dtype)
         else:
             s["corr"] = np.zeros(qf.shape[:3])
         seqs.append(s)
@@ -74,8 +74,9 @@ def varlen_lse(q, k, v, cu_q, cu_k, return_corr=False, **kw):
     return (out, corr) if return_corr else out
 
 
-def p_quantised(s, lse, sm_scale, is_causal):
-    """P [1, Hq, len_q, len_k] of one sequence from its codes, scales and the operator's LSE rows [Hq, len_q]"""
+def p_quantised(s, lse, sm_scale, is_causal, return_arg_err=False):
+    """P [1, Hq, len_q, len_k] of one sequence from its codes, scales and the operator's LSE rows [Hq, len_q]
+    (return_arg_err: and the bound on the kernel's exponent-argument error, bwd_reference.quantised_arg_err)"""
     g = s["qi"].shape[1] // s["ki"].shape[1]
     Sq, Sk = s["qi"].shape[2], s["ki"].shape[2]
     si = np.einsum("bhsd,bhtd->bhst", s["qi"].astype(np.float64), np.repeat(s["ki"].astype(np.float64), g, axis=1), optimize=True)
@@ -83,14 +84,20 @@ def p_quantised(s, lse, sm_scale, is_causal):
     ksr = np.repeat(np.repeat(s["ks"].astype(np.float64), 64, axis=2)[:, :, :Sk], g, axis=1)
     s2 = si * qsr[..., :, None] * ksr[..., None, :]
     lse2 = (lse[None].astype(np.float64) - s["corr"] * sm_scale) * LOG2E
-    p = np.exp2(s2 - lse2[..., None])
-    return np.where(_mask(Sq, Sk, is_causal), p, 0.0)
+    p = np.where(_mask(Sq, Sk, is_causal), np.exp2(s2 - lse2[..., None]), 0.0)
+    if not return_arg_err:
+        return p
+    return p, np.where(_mask(Sq, Sk, is_causal), quantised_arg_err(s2, lse2, s["corr"] * sm_scale), 0.0)
 
 
 def varlen_backward(q, k, v, o, lse, do, cu_q, cu_k, *, dtype="fp16", is_causal=False, sm_scale=None, smooth_k=True,
-                    q_qmax=127, k_qmax=127, dlse=None, p_fn=None, only=None):
+                    q_qmax=127, k_qmax=127, dlse=None, p_fn=None, only=None, return_bound=False):
     """(dq, dk, dv) float64, packed like q / k / v.  `p_fn(b, q_b, k_b, lse_b, sm_scale)` replaces the quantised P of sequence b
-    (q_b / k_b [1, H, len, D]); `only`: the sequences to compute (others stay zero)."""
+    (q_b / k_b [1, H, len, D]); `only`: the sequences to compute (others stay zero).
+    return_bound: (dq, dk, dv, bq, bk, bv) with the per-element bound of bwd_reference.grad_bound, sequence by sequence
+    (0 where the kernel writes exact zeros: tokens in no sequence, sequences without queries or keys); not with p_fn."""
+    if return_bound and p_fn is not None:
+        raise ValueError("return_bound needs the quantised P (p_fn given)")
     cq, ck = [int(x) for x in cu_q], [int(x) for x in cu_k]
     if p_fn is None:
         seqs, sm_scale = intermediates(q, k, v, cu_q, cu_k, dtype=dtype, is_causal=is_causal, sm_scale=sm_scale,
@@ -98,14 +105,21 @@ def varlen_backward(q, k, v, o, lse, do, cu_q, cu_k, *, dtype="fp16", is_causal=
     else:
         seqs, sm_scale = None, (1.0 / q.shape[-1] ** 0.5 if sm_scale is None else sm_scale)
     dq, dk, dv = (np.zeros(x.shape) for x in (q, k, v))
+    bq, bk, bv = (np.zeros(x.shape) for x in (q, k, v))
     for b in range(len(cq) - 1):
         if (only is not None and b not in only) or cq[b + 1] == cq[b] or ck[b + 1] == ck[b]:
             continue  # no queries or no keys: every gradient of the sequence is zero
         qb, kb, vb, ob, dob = (_seq(x, c, b) for x, c in ((q, cq), (k, ck), (v, ck), (o, cq), (do, cq)))
         lb = lse[:, cq[b]:cq[b + 1]]
-        p = p_quantised(seqs[b], lb, sm_scale, is_causal) if p_fn is None else p_fn(b, qb, kb, lb, sm_scale)
         dlb = None if dlse is None else dlse[:, cq[b]:cq[b + 1]][None]
+        if return_bound:
+            p, e = p_quantised(seqs[b], lb, sm_scale, is_causal, return_arg_err=True)
+            bb = grad_bound(p, e, qb, kb, vb, ob, dob, sm_scale=sm_scale, dtype=dtype, dlse=dlb)
+            for out, gb, c in zip((bq, bk, bv), bb, (cq, ck, ck)):
+                out[c[b]:c[b + 1]] = np.transpose(gb[0], (1, 0, 2))
+        else:
+            p = p_quantised(seqs[b], lb, sm_scale, is_causal) if p_fn is None else p_fn(b, qb, kb, lb, sm_scale)
         g = grads_from_p(p, qb, kb, vb, ob, dob, sm_scale=sm_scale, dlse=dlb)
         for out, gb, c in zip((dq, dk, dv), g, (cq, ck, ck)):
             out[c[b]:c[b + 1]] = np.transpose(gb[0], (1, 0, 2))
-    return dq, dk, dv
+    return (dq, dk, dv, bq, bk, bv) if return_bound else (dq, dk, dv)

@@ -84,9 +84,15 @@ def test_smooth_k_invariance():
 
 def test_quantised_p_is_normalised_by_its_own_lse(oracle):
     """int8 codes: P recomputed from the oracle's codes and the oracle's LSE sums to 1 per row (the scores and the LSE
-    correction are the forward's)."""
+    correction are the forward's).  The oracle rounds its smooth-K correction dtype(q . km) from a numpy fp32 sum; the kernels,
+    and so the reference, from their own order (bwd_reference.fwd_corr): the LSE is given the kernels' correction."""
+    from bwd_reference import fwd_corr
     q, k, v = oracle.make_inputs(1, 2, 200, 64, seed=2, Hkv=1, k_bias=0.5)
     for smooth in (False, True):
         o, lse = oracle.lowbit_fa_forward(q, k, v, is_causal=True, smooth_k=smooth, return_lse=True, amax_floor=1e-7)
+        if smooth:
+            km = np.repeat(oracle.mean_seq(k, "fp16"), 2, axis=1)
+            c_orc = oracle.to_storage(np.einsum("bhsd,bhtd->bhs", q.astype(np.float32), km.astype(np.float32)), "fp16")
+            lse = (lse.astype(np.float64) + (fwd_corr(q, km, "fp16") - c_orc) * 64 ** -0.5).astype(np.float32)
         p = recompute_p(q, k, lse, sm_scale=64 ** -0.5, is_causal=True, q_qmax=127, k_qmax=127, smooth_k=smooth)
         assert np.abs(p.sum(-1) - 1).max() <= 1e-5

@@ -2,7 +2,8 @@
 lowbit_quant_fa2_paddle_amd/autograd.py `_VarlenAttentionFn`).
 
 Against `bwd_varlen_reference` (the float64 restatement, fed the operator's own O and LSE) under the bounds of
-test_gpu_backward._assert_close; bit for bit against the dense operator on single sequences; zero gradients outside every
+test_gpu_backward._assert_close and, element by element, of test_gpu_backward._grad_close (bwd_varlen_reference's per-element
+bound, sequence by sequence); bit for bit against the dense operator on single sequences; zero gradients outside every
 sequence; cosine against the true gradient of un-quantised attention.  Whole file 4 s on an MI355X; peak device memory 6.0 GiB
 (torch.cuda.max_memory_allocated: the 64K-token full-size case, q, k, v, o, their gradients and the workspaces at H = 32,
 D = 128)."""
@@ -10,7 +11,7 @@ import numpy as np
 import pytest
 
 from bwd_varlen_reference import varlen_backward, varlen_lse
-from test_gpu_backward import _assert_close
+from test_gpu_backward import _assert_close, _grad_close
 from test_gpu_parity import TDT, _np, _t, dev  # noqa: F401
 
 torch = pytest.importorskip("torch")
@@ -67,8 +68,9 @@ def _covered_keys_nonempty(cu_q, cu_k, total):
 
 
 def _reference(r, dtype, causal, smooth_k, q_qmax=127, k_qmax=127, only=None):
+    """(dq, dk, dv, bq, bk, bv): the reference gradients and their per-element bounds"""
     return varlen_backward(r["q"], r["k"], r["v"], r["o"], r["lse"], r["do"], r["cu_q"], r["cu_k"], dtype=dtype, is_causal=causal,
-                           smooth_k=smooth_k, q_qmax=q_qmax, k_qmax=k_qmax, dlse=r["dlse"], only=only)
+                           smooth_k=smooth_k, q_qmax=q_qmax, k_qmax=k_qmax, dlse=r["dlse"], only=only, return_bound=True)
 
 
 def test_varlen_operator_produces_gradients(dev, oracle):
@@ -150,8 +152,9 @@ def test_varlen_backward_vs_reference(dev, oracle, dtype, D, Hq, Hkv, causal, sm
     r = _run(oracle, dev, lens_q, lens_k, Hq, Hkv, D, dtype=dtype, causal=causal, smooth_k=smooth_k, seed=D + Hq, q_qmax=qq,
              k_qmax=kq, use_dlse=extra.get("use_dlse", False), max_q=extra.get("max_q"), max_k=extra.get("max_k"))
     ref = _reference(r, dtype, causal, smooth_k, qq, kq)
-    for name, got, want in zip(("dq", "dk", "dv"), (r["dq"], r["dk"], r["dv"]), ref):
+    for name, got, want, bnd in zip(("dq", "dk", "dv"), (r["dq"], r["dk"], r["dv"]), ref[:3], ref[3:]):
         _assert_close(got, want, dtype, name)
+        _grad_close(got, want, bnd, name)
     # empty ranges: no queries -> dk = dv = 0 for its keys; no keys -> dq = 0 for its queries
     cq, ck = r["cu_q"], r["cu_k"]
     for b in range(len(lens_q)):
@@ -229,9 +232,10 @@ def test_tokens_outside_sequences_and_past_the_cut_get_zero_gradient(dev, oracle
     for x in ("dq", "dk", "dv"):
         assert np.all(np.isfinite(r[x]))
     ref = _reference(r, "fp16", False, True, only=(0, 2))
-    for name, got, want, c in zip(("dq", "dk", "dv"), (r["dq"], r["dk"], r["dv"]), ref, (cq, ck, ck)):
+    for name, got, want, bnd, c in zip(("dq", "dk", "dv"), (r["dq"], r["dk"], r["dv"]), ref[:3], ref[3:], (cq, ck, ck)):
         for b in (0, 2):
             _assert_close(got[c[b]:c[b + 1]], want[c[b]:c[b + 1]], "fp16", f"{name} seq {b}")
+            _grad_close(got[c[b]:c[b + 1]], want[c[b]:c[b + 1]], bnd[c[b]:c[b + 1]], f"{name}_seq{b}")
 
 
 @pytest.mark.parametrize("causal", [False, True])
