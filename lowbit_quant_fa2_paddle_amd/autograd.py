@@ -27,6 +27,36 @@ def _kernel_operand(t, D):
     return t
 
 
+def _pad_operands(q, k, v, o, do):
+    """-> (D, kernel operands of q, k, v, o, dO): the head dim zero-padded to the D = 64 / 128 the backward kernels run on"""
+    if do is None:
+        do = torch.zeros_like(o)
+    D = 64 if q.shape[-1] <= 64 else 128
+    return D, tuple(_kernel_operand(t, D) for t in (q, k, v, o, do.to(o.dtype)))
+
+
+def _run_backward(fn, workspace_bytes, shape, cu, st, D, operands, lse, dlse, cfg, Dg):
+    """What the dense and the packed backward share once the problem is described: gradient buffers, dLSE as contiguous fp32, the
+    workspace, the dtype code, the call and the trim back to the caller's head dim Dg.  `fn` / `workspace_bytes`: the entry
+    point and its size query; `shape`: their integer arguments before D; `cu`: the offset tables of a packed batch (else empty);
+    `st(t)`: the stride array of a tensor.  -> (dq, dk, dv)"""
+    is_causal, sm_scale, smooth_k, q_qmax, k_qmax = cfg
+    qp, kp, vp = operands[:3]
+    # written completely by the kernels (packed batch: tokens outside every sequence get zeros there)
+    dq, dk, dv = (torch.empty(t.shape, dtype=t.dtype, device=t.device) for t in (qp, kp, vp))
+    if dlse is not None:
+        dlse = dlse.to(torch.float32).contiguous()
+    ws_bytes = workspace_bytes(*shape, D, q_qmax, 1 if smooth_k else 0)
+    ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=qp.device)
+    code = _lib.LBFA_F16 if qp.dtype == torch.float16 else _lib.LBFA_BF16
+    with torch.cuda.device(qp.device):
+        _lib.check(fn(*(t.data_ptr() for t in operands), code, lse.data_ptr(), dlse.data_ptr() if dlse is not None else None,
+                      dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), *(t.data_ptr() for t in cu), ws.data_ptr(), ws_bytes, *shape, D,
+                      *(st(t) for t in operands), st(dq), st(dk), st(dv), float(sm_scale), int(q_qmax), int(k_qmax),
+                      1 if is_causal else 0, 1 if smooth_k else 0, torch.cuda.current_stream(qp.device).cuda_stream))
+    return (dq[..., :Dg], dk[..., :Dg], dv[..., :Dg]) if D != Dg else (dq, dk, dv)
+
+
 class _AttentionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, forward, cfg):
@@ -41,35 +71,17 @@ class _AttentionFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, do, dlse):
         q, k, v, o, lse = ctx.saved_tensors
-        layout, is_causal, sm_scale, smooth_k, q_qmax, k_qmax = ctx.cfg
+        layout, *cfg = ctx.cfg
         if do is None and dlse is None:
             return None, None, None, None, None
-        if do is None:
-            do = torch.zeros_like(o)
-        Dg = q.shape[-1]
-        D = 64 if Dg <= 64 else 128
-        qp, kp, vp, op, dop = (_kernel_operand(t, D) for t in (q, k, v, o, do.to(o.dtype)))
-        dq = torch.empty(qp.shape, dtype=q.dtype, device=q.device)
-        dk = torch.empty(kp.shape, dtype=k.dtype, device=k.device)
-        dv = torch.empty(vp.shape, dtype=v.dtype, device=v.device)
+        D, operands = _pad_operands(q, k, v, o, do)
+        qp, kp = operands[:2]
         (B, Hq, Sq), _ = _qpb._bhs(qp.shape, qp.stride(), layout)
         (_, Hkv, Sk), _ = _qpb._bhs(kp.shape, kp.stride(), layout)
         st = lambda t: _lib.strides3(_qpb._bhs(t.shape, t.stride(), layout)[1])
-        if dlse is not None:
-            dlse = dlse.to(torch.float32).contiguous()
         lib = _lib.load()
-        ws_bytes = lib.lbfa_backward_workspace_bytes(B, Hq, Hkv, Sq, Sk, D, q_qmax, 1 if smooth_k else 0)
-        ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=q.device)
-        code = _lib.LBFA_F16 if q.dtype == torch.float16 else _lib.LBFA_BF16
-        with torch.cuda.device(q.device):
-            _lib.check(lib.lbfa_backward(qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), op.data_ptr(), dop.data_ptr(), code,
-                                         lse.data_ptr(), dlse.data_ptr() if dlse is not None else None,
-                                         dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ws.data_ptr(), ws_bytes,
-                                         B, Hq, Hkv, Sq, Sk, D, st(qp), st(kp), st(vp), st(op), st(dop), st(dq), st(dk), st(dv),
-                                         float(sm_scale), int(q_qmax), int(k_qmax), 1 if is_causal else 0,
-                                         1 if smooth_k else 0, torch.cuda.current_stream(q.device).cuda_stream), lib)
-        if D != Dg:
-            dq, dk, dv = dq[..., :Dg], dk[..., :Dg], dv[..., :Dg]
+        dq, dk, dv = _run_backward(lib.lbfa_backward, lib.lbfa_backward_workspace_bytes, (B, Hq, Hkv, Sq, Sk), (), st, D, operands,
+                                   lse, dlse, cfg, q.shape[-1])
         return dq, dk, dv, None, None
 
 
@@ -93,39 +105,18 @@ class _VarlenAttentionFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, do, dlse):
         q, k, v, o, lse, cu_q, cu_k = ctx.saved_tensors
-        max_q, max_k, is_causal, sm_scale, smooth_k, q_qmax, k_qmax = ctx.cfg
+        max_q, max_k, *cfg = ctx.cfg
         if do is None and dlse is None:
             return None, None, None, None, None, None, None
-        if do is None:
-            do = torch.zeros_like(o)
-        Dg = q.shape[-1]
-        D = 64 if Dg <= 64 else 128
-        qp, kp, vp, op, dop = (_kernel_operand(t, D) for t in (q, k, v, o, do.to(o.dtype)))
-        # written completely by the kernels: tokens outside every sequence get zeros there
-        dq = torch.empty(qp.shape, dtype=q.dtype, device=q.device)
-        dk = torch.empty(kp.shape, dtype=k.dtype, device=k.device)
-        dv = torch.empty(vp.shape, dtype=v.dtype, device=v.device)
-        total_q, Hq, _ = qp.shape
-        total_k, Hkv, _ = kp.shape
+        D, operands = _pad_operands(q, k, v, o, do)
+        total_q, Hq, _ = operands[0].shape
+        total_k, Hkv, _ = operands[1].shape
         B = cu_q.shape[0] - 1
         st = lambda t: _lib.strides2((t.stride(1), t.stride(0)))  # {head, token}
-        if dlse is not None:
-            dlse = dlse.to(torch.float32).contiguous()
         lib = _lib.load()
-        ws_bytes = lib.lbfa_backward_varlen_workspace_bytes(B, Hq, Hkv, total_q, total_k, max_q, max_k, D, q_qmax,
-                                                            1 if smooth_k else 0)
-        ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=q.device)
-        code = _lib.LBFA_F16 if q.dtype == torch.float16 else _lib.LBFA_BF16
-        with torch.cuda.device(q.device):
-            _lib.check(lib.lbfa_backward_varlen(qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), op.data_ptr(), dop.data_ptr(), code,
-                                                lse.data_ptr(), dlse.data_ptr() if dlse is not None else None,
-                                                dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), cu_q.data_ptr(), cu_k.data_ptr(),
-                                                ws.data_ptr(), ws_bytes, B, Hq, Hkv, total_q, total_k, max_q, max_k, D,
-                                                st(qp), st(kp), st(vp), st(op), st(dop), st(dq), st(dk), st(dv),
-                                                float(sm_scale), int(q_qmax), int(k_qmax), 1 if is_causal else 0,
-                                                1 if smooth_k else 0, torch.cuda.current_stream(q.device).cuda_stream), lib)
-        if D != Dg:
-            dq, dk, dv = dq[..., :Dg], dk[..., :Dg], dv[..., :Dg]
+        dq, dk, dv = _run_backward(lib.lbfa_backward_varlen, lib.lbfa_backward_varlen_workspace_bytes,
+                                   (B, Hq, Hkv, total_q, total_k, max_q, max_k), (cu_q, cu_k), st, D, operands, lse, dlse, cfg,
+                                   q.shape[-1])
         return dq, dk, dv, None, None, None, None
 
 

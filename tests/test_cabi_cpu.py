@@ -6,6 +6,8 @@ import re
 
 import pytest
 
+from cabi_calls import A, check_table
+
 from conftest import ROOT
 
 HEADER = os.path.join(ROOT, "include", "lowbit_fa.h")
@@ -169,3 +171,498 @@ def test_product_does_not_import_oracle():
             if f.endswith((".py", ".hip", ".h", ".cpp")):
                 txt = open(os.path.join(dirpath, f)).read()
                 assert "import oracle" not in txt and "from oracle" not in txt, os.path.join(dirpath, f)
+
+
+# status and full text of lbfa_last_error() for calls with one thing wrong (tests/cabi_calls.py): every check of every entry
+# point that can fire without a GPU, the 2 GiB operand windows on both sides of their limit (the largest accepted stride or
+# length is shown by the NEXT check firing: the grid-size check, which needs integers only).  (name, overrides, message)
+SINGLE_FAULT = [
+    ("lbfa_absmax", dict(x=None),
+     'lbfa_absmax: null pointer'),
+    ("lbfa_absmax", dict(out=None),
+     'lbfa_absmax: null pointer'),
+    ("lbfa_absmax", dict(sx=None),
+     'lbfa_absmax: null pointer'),
+    ("lbfa_absmax", dict(B=0),
+     'lbfa_absmax: empty tensor or head_dim 64 not a multiple of 8'),
+    ("lbfa_absmax", dict(D=36),
+     'lbfa_absmax: empty tensor or head_dim 36 not a multiple of 8'),
+    ("lbfa_absmax", dict(D=0),
+     'lbfa_absmax: empty tensor or head_dim 0 not a multiple of 8'),
+    ("lbfa_absmax", dict(dtype=2),
+     'Input tensors must be in dtype of float16 or bfloat16'),
+    ("lbfa_absmax", dict(x=A(2)),
+     'lbfa_absmax: x must be 16-byte aligned with strides that are multiples of 8 elements'),
+    ("lbfa_absmax", dict(sx=(1024, 512, 60)),
+     'lbfa_absmax: x must be 16-byte aligned with strides that are multiples of 8 elements'),
+    ("lbfa_mean_seq", dict(x=None),
+     'lbfa_mean_seq: null pointer'),
+    ("lbfa_mean_seq", dict(mean_out=None),
+     'lbfa_mean_seq: null pointer'),
+    ("lbfa_mean_seq", dict(workspace=None),
+     'lbfa_mean_seq: null pointer'),
+    ("lbfa_mean_seq", dict(sx=None),
+     'lbfa_mean_seq: null pointer'),
+    ("lbfa_mean_seq", dict(D=96),
+     'Unsupported head_dim: 96 (or empty tensor 1x2x8)'),
+    ("lbfa_mean_seq", dict(S=0),
+     'Unsupported head_dim: 64 (or empty tensor 1x2x0)'),
+    ("lbfa_mean_seq", dict(dtype=5),
+     'Input tensors must be in dtype of float16 or bfloat16'),
+    ("lbfa_mean_seq", dict(workspace_bytes=0),
+     'lbfa_mean_seq: workspace too small'),
+    ("lbfa_mean_seq", dict(x=A(8)),
+     'lbfa_mean_seq: x must be 16-byte aligned with strides that are multiples of 8 elements'),
+    ("lbfa_mean_seq", dict(sx=(1024, 512, 60)),
+     'lbfa_mean_seq: x must be 16-byte aligned with strides that are multiples of 8 elements'),
+    ("lbfa_quant_per_block", dict(x=None),
+     'lbfa_quant_per_block: null pointer'),
+    ("lbfa_quant_per_block", dict(out=None),
+     'lbfa_quant_per_block: null pointer'),
+    ("lbfa_quant_per_block", dict(scale=None),
+     'lbfa_quant_per_block: null pointer'),
+    ("lbfa_quant_per_block", dict(sx=None),
+     'lbfa_quant_per_block: null pointer'),
+    ("lbfa_quant_per_block", dict(sout=None),
+     'lbfa_quant_per_block: null pointer'),
+    ("lbfa_quant_per_block", dict(D=96),
+     'Unsupported head_dim: 96 (or empty tensor 1x2x8)'),
+    ("lbfa_quant_per_block", dict(B=0),
+     'Unsupported head_dim: 64 (or empty tensor 0x2x8)'),
+    ("lbfa_quant_per_block", dict(dtype=5),
+     'Input tensors must be in dtype of float16 or bfloat16'),
+    ("lbfa_quant_per_block", dict(qmax=15),
+     'lbfa_quant_per_block: qmax must be 127 (int8) or 7 (int4 range), got 15'),
+    ("lbfa_quant_per_block", dict(blk=32),
+     'lbfa_quant_per_block: blk must be 128 or 64, got 32'),
+    ("lbfa_quant_per_block", dict(mean=A(0), mean_group=0),
+     'lbfa_quant_per_block: bad mean_group 0 for H=2'),
+    ("lbfa_quant_per_block", dict(mean=A(0), mean_group=3),
+     'lbfa_quant_per_block: bad mean_group 3 for H=2'),
+    ("lbfa_quant_per_block", dict(rowdot_vec=A(0)),
+     'lbfa_quant_per_block: rowdot_vec needs rowdot_out and a rowdot_group dividing H'),
+    ("lbfa_quant_per_block", dict(rowdot_vec=A(0), rowdot_out=A(0), rowdot_group=3),
+     'lbfa_quant_per_block: rowdot_vec needs rowdot_out and a rowdot_group dividing H'),
+    ("lbfa_quant_per_block", dict(x=A(8)),
+     'lbfa_quant_per_block: x must be 16-byte aligned with strides that are multiples of 8 elements'),
+    ("lbfa_quant_per_block", dict(sx=(1024, 512, 60)),
+     'lbfa_quant_per_block: x must be 16-byte aligned with strides that are multiples of 8 elements'),
+    ("lbfa_quant_per_block", dict(out=A(4)),
+     'lbfa_quant_per_block: out must be 8-byte aligned with strides that are multiples of 8'),
+    ("lbfa_quant_per_block", dict(sout=(1024, 512, 60)),
+     'lbfa_quant_per_block: out must be 8-byte aligned with strides that are multiples of 8'),
+    ("lbfa_quant_per_block_varlen", dict(cu_scale=None),
+     'lbfa_quant_per_block_varlen: null pointer'),
+    ("lbfa_quant_per_block_varlen", dict(x=None),
+     'lbfa_quant_per_block_varlen: null pointer'),
+    ("lbfa_quant_per_block_varlen", dict(cu=None),
+     'lbfa_quant_per_block_varlen: null pointer'),
+    ("lbfa_quant_per_block_varlen", dict(sout=None),
+     'lbfa_quant_per_block_varlen: null pointer'),
+    ("lbfa_quant_per_block_varlen", dict(D=96),
+     'Unsupported head_dim: 96 (or empty batch 1x2x8)'),
+    ("lbfa_quant_per_block_varlen", dict(max_seqlen=0),
+     'Unsupported head_dim: 64 (or empty batch 1x2x0)'),
+    ("lbfa_quant_per_block_varlen", dict(dtype=5),
+     'Input tensors must be in dtype of float16 or bfloat16'),
+    ("lbfa_quant_per_block_varlen", dict(qmax=15),
+     'lbfa_quant_per_block_varlen: qmax must be 127 (int8) or 7 (int4 range), got 15'),
+    ("lbfa_quant_per_block_varlen", dict(blk=32),
+     'lbfa_quant_per_block_varlen: blk must be 128 or 64, got 32'),
+    ("lbfa_quant_per_block_varlen", dict(mean=A(0), mean_group=3),
+     'lbfa_quant_per_block_varlen: bad mean_group 3 for H=2'),
+    ("lbfa_quant_per_block_varlen", dict(x=A(8)),
+     'lbfa_quant_per_block_varlen: x must be 16-byte aligned with strides that are multiples of 8 elements'),
+    ("lbfa_quant_per_block_varlen", dict(sx=(64, 60)),
+     'lbfa_quant_per_block_varlen: x must be 16-byte aligned with strides that are multiples of 8 elements'),
+    ("lbfa_quant_per_block_varlen", dict(out=A(4)),
+     'lbfa_quant_per_block_varlen: out must be 8-byte aligned with strides that are multiples of 8'),
+    ("lbfa_quant_per_block_varlen", dict(sout=(64, 60)),
+     'lbfa_quant_per_block_varlen: out must be 8-byte aligned with strides that are multiples of 8'),
+    ("lbfa_quant_v_fp8", dict(v=None),
+     'lbfa_quant_v_fp8: null pointer'),
+    ("lbfa_quant_v_fp8", dict(v_fp8=None),
+     'lbfa_quant_v_fp8: null pointer'),
+    ("lbfa_quant_v_fp8", dict(v_scale=None),
+     'lbfa_quant_v_fp8: null pointer'),
+    ("lbfa_quant_v_fp8", dict(sv=None),
+     'lbfa_quant_v_fp8: null pointer'),
+    ("lbfa_quant_v_fp8", dict(D=96),
+     'Unsupported head_dim: 96 (or empty tensor 1x2x8)'),
+    ("lbfa_quant_v_fp8", dict(H=0),
+     'Unsupported head_dim: 64 (or empty tensor 1x0x8)'),
+    ("lbfa_quant_v_fp8", dict(dtype=5),
+     'Input tensors must be in dtype of float16 or bfloat16'),
+    ("lbfa_quant_v_fp8", dict(v=A(8)),
+     'lbfa_quant_v_fp8: v / v_fp8 must be 16-byte aligned, strides multiples of 8 elements'),
+    ("lbfa_quant_v_fp8", dict(v_fp8=A(8)),
+     'lbfa_quant_v_fp8: v / v_fp8 must be 16-byte aligned, strides multiples of 8 elements'),
+    ("lbfa_quant_v_fp8", dict(sv=(1024, 512, 60)),
+     'lbfa_quant_v_fp8: v / v_fp8 must be 16-byte aligned, strides multiples of 8 elements'),
+    ("lbfa_cast_bf16_to_f16", dict(src=None),
+     'lbfa_cast_bf16_to_f16: null pointer'),
+    ("lbfa_cast_bf16_to_f16", dict(sdst=None),
+     'lbfa_cast_bf16_to_f16: null pointer'),
+    ("lbfa_cast_bf16_to_f16", dict(D=36),
+     'lbfa_cast_bf16_to_f16: bad shape (D must be a multiple of 8)'),
+    ("lbfa_cast_bf16_to_f16", dict(B=0),
+     'lbfa_cast_bf16_to_f16: bad shape (D must be a multiple of 8)'),
+    ("lbfa_cast_bf16_to_f16", dict(src=A(8)),
+     'lbfa_cast_bf16_to_f16: tensors must be 16-byte aligned, strides multiples of 8 elements'),
+    ("lbfa_cast_bf16_to_f16", dict(dst=A(8)),
+     'lbfa_cast_bf16_to_f16: tensors must be 16-byte aligned, strides multiples of 8 elements'),
+    ("lbfa_cast_bf16_to_f16", dict(ssrc=(1024, 512, 60)),
+     'lbfa_cast_bf16_to_f16: tensors must be 16-byte aligned, strides multiples of 8 elements'),
+    ("lbfa_cast_bf16_to_f16", dict(sdst=(1024, 512, 60)),
+     'lbfa_cast_bf16_to_f16: tensors must be 16-byte aligned, strides multiples of 8 elements'),
+    ("lbfa_attn_fwd", dict(q=None),
+     'lbfa_attn_fwd: null pointer'),
+    ("lbfa_attn_fwd", dict(q_scale=None),
+     'lbfa_attn_fwd: null pointer'),
+    ("lbfa_attn_fwd", dict(k_scale=None),
+     'lbfa_attn_fwd: null pointer'),
+    ("lbfa_attn_fwd", dict(sq=None),
+     'lbfa_attn_fwd: null pointer'),
+    ("lbfa_attn_fwd", dict(so=None),
+     'lbfa_attn_fwd: null pointer'),
+    ("lbfa_attn_fwd", dict(Sq=0),
+     'lbfa_attn_fwd: empty tensor'),
+    ("lbfa_attn_fwd", dict(Hkv=0),
+     'lbfa_attn_fwd: empty tensor'),
+    ("lbfa_attn_fwd", dict(D=96),
+     'Unsupported head_dim: 96'),
+    ("lbfa_attn_fwd", dict(Hq=3),
+     'num_qo_heads (3) must be divisible by num_kv_heads (2)'),
+    ("lbfa_attn_fwd", dict(v_dtype=1),
+     'lbfa_attn_fwd: v must be float16 (cast bfloat16 with lbfa_cast_bf16_to_f16, the `v.to(float16)` of the reference) or e4m3'),
+    ("lbfa_attn_fwd", dict(v_dtype=7),
+     'lbfa_attn_fwd: bad v_dtype 7'),
+    ("lbfa_attn_fwd", dict(o_dtype=2),
+     'lbfa_attn_fwd: bad o_dtype 2'),
+    ("lbfa_attn_fwd", dict(v_dtype=2),
+     'lbfa_attn_fwd: v_scale is required for fp8 V'),
+    ("lbfa_attn_fwd", dict(sv=None),
+     'lbfa_attn_fwd: strides_v is required for fp16 V'),
+    ("lbfa_attn_fwd", dict(causal=1, Sk=16),
+     'qo_len and kv_len must be equal for causal attention'),
+    ("lbfa_attn_fwd", dict(q=A(8)),
+     'lbfa_attn_fwd: q/k/v must be 16-byte aligned and o 8-byte aligned'),
+    ("lbfa_attn_fwd", dict(k=A(8)),
+     'lbfa_attn_fwd: q/k/v must be 16-byte aligned and o 8-byte aligned'),
+    ("lbfa_attn_fwd", dict(v=A(8)),
+     'lbfa_attn_fwd: q/k/v must be 16-byte aligned and o 8-byte aligned'),
+    ("lbfa_attn_fwd", dict(o=A(4)),
+     'lbfa_attn_fwd: q/k/v must be 16-byte aligned and o 8-byte aligned'),
+    ("lbfa_attn_fwd", dict(sq=(1024, 512, 72)),
+     'lbfa_attn_fwd: q/k strides must be multiples of 16 elements'),
+    ("lbfa_attn_fwd", dict(sk=(1024, 512, 72)),
+     'lbfa_attn_fwd: q/k strides must be multiples of 16 elements'),
+    ("lbfa_attn_fwd", dict(sv=(1024, 512, 60)),
+     'lbfa_attn_fwd: v strides must be multiples of 8 elements'),
+    ("lbfa_attn_fwd", dict(so=(1024, 512, 62)),
+     'lbfa_attn_fwd: o strides must be multiples of 4 elements'),
+    ("lbfa_attn_fwd", dict(sq=(1024, 512, 15790336)),
+     'lbfa_attn_fwd: per-(batch,head) operand window exceeds 2 GiB (seq stride x length too large)'),
+    ("lbfa_attn_fwd", dict(sq=(1024, 512, 15790320), B=65536, Hq=65536, Hkv=1),
+     'lbfa_attn_fwd: grid too large'),
+    ("lbfa_attn_fwd", dict(sk=(1024, 512, 15790336)),
+     'lbfa_attn_fwd: per-(batch,head) operand window exceeds 2 GiB (seq stride x length too large)'),
+    ("lbfa_attn_fwd", dict(sk=(1024, 512, 15790320), B=65536, Hq=65536, Hkv=1),
+     'lbfa_attn_fwd: grid too large'),
+    ("lbfa_attn_fwd", dict(sv=(1024, 512, 7895160)),
+     'lbfa_attn_fwd: per-(batch,head) operand window exceeds 2 GiB (seq stride x length too large)'),
+    ("lbfa_attn_fwd", dict(sv=(1024, 512, 7895152), B=65536, Hq=65536, Hkv=1),
+     'lbfa_attn_fwd: grid too large'),
+    ("lbfa_attn_fwd", dict(v_dtype=2, v_scale=A(0), sv=None, sk=(1024, 512, 16), Sk=33554304),
+     'lbfa_attn_fwd: per-(batch,head) operand window exceeds 2 GiB (seq stride x length too large)'),
+    ("lbfa_attn_fwd", dict(v_dtype=2, v_scale=A(0), sv=None, sk=(1024, 512, 16), Sk=33554303, B=65536, Hq=65536, Hkv=1),
+     'lbfa_attn_fwd: grid too large'),
+    ("lbfa_attn_fwd", dict(B=65536, Hq=65536, Hkv=1),
+     'lbfa_attn_fwd: grid too large'),
+    ("lbfa_forward", dict(q=None),
+     'lbfa_forward: null pointer'),
+    ("lbfa_forward", dict(workspace=None),
+     'lbfa_forward: null pointer'),
+    ("lbfa_forward", dict(sv=None),
+     'lbfa_forward: null pointer'),
+    ("lbfa_forward", dict(B=0),
+     'lbfa_forward: empty tensor'),
+    ("lbfa_forward", dict(Sk=0),
+     'lbfa_forward: empty tensor'),
+    ("lbfa_forward", dict(D=36),
+     'Unsupported head_dim: 36'),
+    ("lbfa_forward", dict(D=136),
+     'Unsupported head_dim: 136'),
+    ("lbfa_forward", dict(Hq=3),
+     'num_qo_heads (3) must be divisible by num_kv_heads (2)'),
+    ("lbfa_forward", dict(workspace_bytes=16),
+     'lbfa_forward: workspace too small (16 < 2560)'),
+    ("lbfa_forward", dict(workspace=A(8)),
+     'lbfa_forward: workspace must be 16-byte aligned'),
+    ("lbfa_forward", dict(dtype=5),
+     'Input tensors must be in dtype of float16 or bfloat16'),
+    ("lbfa_forward", dict(q_qmax=15),
+     'lbfa_forward: q_qmax must be 127 (int8) or 7 (int4 range), got 15'),
+    ("lbfa_forward", dict(k_qmax=15),
+     'lbfa_forward: k_qmax must be 127 (int8) or 7 (int4 range), got 15'),
+    ("lbfa_forward", dict(q=A(8)),
+     'lbfa_forward: q must be 16-byte aligned with strides that are multiples of 8 elements'),
+    ("lbfa_forward", dict(sq=(1024, 512, 60)),
+     'lbfa_forward: q must be 16-byte aligned with strides that are multiples of 8 elements'),
+    ("lbfa_forward", dict(k=A(8)),
+     'lbfa_forward: k must be 16-byte aligned with strides that are multiples of 8 elements'),
+    ("lbfa_forward", dict(sk=(1024, 512, 60)),
+     'lbfa_forward: k must be 16-byte aligned with strides that are multiples of 8 elements'),
+    ("lbfa_forward", dict(v=A(8)),
+     'lbfa_forward: v must be 16-byte aligned with strides that are multiples of 8 elements'),
+    ("lbfa_forward", dict(sv=(1024, 512, 60)),
+     'lbfa_forward: v must be 16-byte aligned with strides that are multiples of 8 elements'),
+    ("lbfa_forward", dict(o=A(4)),
+     'lbfa_forward: o must be 8-byte aligned with strides that are multiples of 4 elements'),
+    ("lbfa_forward", dict(so=(1024, 512, 62)),
+     'lbfa_forward: o must be 8-byte aligned with strides that are multiples of 4 elements'),
+    ("lbfa_forward", dict(causal=1, Sk=16),
+     'qo_len and kv_len must be equal for causal attention'),
+    ("lbfa_forward", dict(sq=(1024, 512, 7895160)),
+     'lbfa_forward: per-(batch,head) operand window exceeds 2 GiB'),
+    ("lbfa_forward", dict(sq=(1024, 512, 7895152), workspace_bytes=4611686018427387904, B=65536, Hq=65536, Hkv=1),
+     'lbfa_forward: grid too large'),
+    ("lbfa_forward", dict(sv=(1024, 512, 7895160)),
+     'lbfa_forward: per-(batch,head) operand window exceeds 2 GiB'),
+    ("lbfa_forward", dict(sv=(1024, 512, 7895152), workspace_bytes=4611686018427387904, B=65536, Hq=65536, Hkv=1),
+     'lbfa_forward: grid too large'),
+    ("lbfa_forward", dict(Sk=33554303, workspace_bytes=4611686018427387904, sv=(1024, 512, 8)),
+     'lbfa_forward: per-(batch,head) operand window exceeds 2 GiB'),
+    ("lbfa_forward", dict(Sk=33554302, workspace_bytes=4611686018427387904, sv=(1024, 512, 8), B=65536, Hq=65536, Hkv=1),
+     'lbfa_forward: grid too large'),
+    ("lbfa_forward", dict(Sk=33554303, workspace_bytes=4611686018427387904, pv_fp8=1),
+     'lbfa_forward: per-(batch,head) operand window exceeds 2 GiB'),
+    ("lbfa_forward", dict(Sk=33554302, workspace_bytes=4611686018427387904, pv_fp8=1, sv=(1024, 512, 8796093022208), B=65536, Hq=65536, Hkv=1),
+     'lbfa_forward: grid too large'),
+    ("lbfa_forward", dict(D=40, sq=(1024, 512, 7895160)),
+     'lbfa_forward: per-(batch,head) operand window exceeds 2 GiB'),
+    ("lbfa_forward", dict(D=40, sq=(1024, 512, 7895152), workspace_bytes=4611686018427387904, B=65536, Hq=65536, Hkv=1),
+     'lbfa_forward: grid too large'),
+    ("lbfa_forward", dict(workspace_bytes=4611686018427387904, B=65536, Hq=65536, Hkv=1),
+     'lbfa_forward: grid too large'),
+    ("lbfa_sdpa_fwd", dict(q=None),
+     'lbfa_sdpa_fwd: null pointer'),
+    ("lbfa_sdpa_fwd", dict(so=None),
+     'lbfa_sdpa_fwd: null pointer'),
+    ("lbfa_sdpa_fwd", dict(Sq=0),
+     'lbfa_sdpa_fwd: empty tensor'),
+    ("lbfa_sdpa_fwd", dict(D=36),
+     'Unsupported head_dim: 36'),
+    ("lbfa_sdpa_fwd", dict(Hq=3),
+     'num_qo_heads (3) must be divisible by num_kv_heads (2)'),
+    ("lbfa_sdpa_fwd", dict(dtype=2),
+     'Input tensors must be in dtype of float16 or bfloat16'),
+    ("lbfa_sdpa_fwd", dict(causal=1, Sk=16),
+     'qo_len and kv_len must be equal for causal attention'),
+    ("lbfa_sdpa_fwd", dict(sm_scale=0.0),
+     'lbfa_sdpa_fwd: sm_scale must be positive (the row maximum is tracked on the unscaled scores)'),
+    ("lbfa_sdpa_fwd", dict(sm_scale=float("nan")),
+     'lbfa_sdpa_fwd: sm_scale must be positive (the row maximum is tracked on the unscaled scores)'),
+    ("lbfa_sdpa_fwd", dict(q=A(8)),
+     'lbfa_sdpa_fwd: q/k/v must be 16-byte aligned and o 8-byte aligned'),
+    ("lbfa_sdpa_fwd", dict(v=A(8)),
+     'lbfa_sdpa_fwd: q/k/v must be 16-byte aligned and o 8-byte aligned'),
+    ("lbfa_sdpa_fwd", dict(o=A(4)),
+     'lbfa_sdpa_fwd: q/k/v must be 16-byte aligned and o 8-byte aligned'),
+    ("lbfa_sdpa_fwd", dict(sq=(1024, 512, 60)),
+     'lbfa_sdpa_fwd: q/k/v strides must be multiples of 8 elements'),
+    ("lbfa_sdpa_fwd", dict(sv=(1024, 512, 60)),
+     'lbfa_sdpa_fwd: q/k/v strides must be multiples of 8 elements'),
+    ("lbfa_sdpa_fwd", dict(so=(1024, 512, 62)),
+     'lbfa_sdpa_fwd: o strides must be multiples of 4 elements'),
+    ("lbfa_sdpa_fwd", dict(sq=(1024, 512, 7895160)),
+     'lbfa_sdpa_fwd: per-(batch,head) operand window exceeds 2 GiB'),
+    ("lbfa_sdpa_fwd", dict(sq=(1024, 512, 7895152), B=65536, Hq=65536, Hkv=1),
+     'lbfa_sdpa_fwd: grid too large'),
+    ("lbfa_sdpa_fwd", dict(sk=(1024, 512, 7895160)),
+     'lbfa_sdpa_fwd: per-(batch,head) operand window exceeds 2 GiB'),
+    ("lbfa_sdpa_fwd", dict(sk=(1024, 512, 7895152), B=65536, Hq=65536, Hkv=1),
+     'lbfa_sdpa_fwd: grid too large'),
+    ("lbfa_sdpa_fwd", dict(sv=(1024, 512, 7895160)),
+     'lbfa_sdpa_fwd: per-(batch,head) operand window exceeds 2 GiB'),
+    ("lbfa_sdpa_fwd", dict(sv=(1024, 512, 7895152), B=65536, Hq=65536, Hkv=1),
+     'lbfa_sdpa_fwd: grid too large'),
+    ("lbfa_sdpa_fwd", dict(D=40, sq=(1024, 512, 7895168)),
+     'lbfa_sdpa_fwd: per-(batch,head) operand window exceeds 2 GiB'),
+    ("lbfa_sdpa_fwd", dict(D=40, sq=(1024, 512, 7895160), B=65536, Hq=65536, Hkv=1),
+     'lbfa_sdpa_fwd: grid too large'),
+    ("lbfa_sdpa_fwd", dict(B=65536, Hq=65536, Hkv=1),
+     'lbfa_sdpa_fwd: grid too large'),
+    ("lbfa_attn_fwd_varlen", dict(cu_qscale=None),
+     'lbfa_attn_fwd_varlen: null pointer'),
+    ("lbfa_attn_fwd_varlen", dict(cu_kscale=None),
+     'lbfa_attn_fwd_varlen: null pointer'),
+    ("lbfa_attn_fwd_varlen", dict(q=None),
+     'lbfa_attn_fwd_varlen: null pointer'),
+    ("lbfa_attn_fwd_varlen", dict(q_scale=None),
+     'lbfa_attn_fwd_varlen: null pointer'),
+    ("lbfa_attn_fwd_varlen", dict(cu_k=None),
+     'lbfa_attn_fwd_varlen: null pointer'),
+    ("lbfa_attn_fwd_varlen", dict(sv=None),
+     'lbfa_attn_fwd_varlen: null pointer'),
+    ("lbfa_attn_fwd_varlen", dict(B=0),
+     'lbfa_attn_fwd_varlen: empty batch'),
+    ("lbfa_attn_fwd_varlen", dict(max_k=0),
+     'lbfa_attn_fwd_varlen: empty batch'),
+    ("lbfa_attn_fwd_varlen", dict(D=96),
+     'Unsupported head_dim: 96'),
+    ("lbfa_attn_fwd_varlen", dict(Hq=3),
+     'num_qo_heads (3) must be divisible by num_kv_heads (2)'),
+    ("lbfa_attn_fwd_varlen", dict(v_dtype=1),
+     'lbfa_attn_fwd_varlen: v must be float16 (cast bfloat16 with lbfa_cast_bf16_to_f16)'),
+    ("lbfa_attn_fwd_varlen", dict(v_dtype=2),
+     'lbfa_attn_fwd_varlen: v must be float16 (cast bfloat16 with lbfa_cast_bf16_to_f16)'),
+    ("lbfa_attn_fwd_varlen", dict(o_dtype=2),
+     'lbfa_attn_fwd_varlen: bad o_dtype 2'),
+    ("lbfa_attn_fwd_varlen", dict(q=A(8)),
+     'lbfa_attn_fwd_varlen: q/k/v must be 16-byte aligned and o 8-byte aligned'),
+    ("lbfa_attn_fwd_varlen", dict(o=A(4)),
+     'lbfa_attn_fwd_varlen: q/k/v must be 16-byte aligned and o 8-byte aligned'),
+    ("lbfa_attn_fwd_varlen", dict(sq=(72, 128)),
+     'lbfa_attn_fwd_varlen: q/k strides must be multiples of 16 elements'),
+    ("lbfa_attn_fwd_varlen", dict(sk=(72, 128)),
+     'lbfa_attn_fwd_varlen: q/k strides must be multiples of 16 elements'),
+    ("lbfa_attn_fwd_varlen", dict(sv=(64, 60)),
+     'lbfa_attn_fwd_varlen: v strides must be multiples of 8 elements'),
+    ("lbfa_attn_fwd_varlen", dict(so=(62, 128)),
+     'lbfa_attn_fwd_varlen: o strides must be multiples of 4 elements'),
+    ("lbfa_attn_fwd_varlen", dict(sq=(64, 15790336)),
+     'lbfa_attn_fwd_varlen: per-sequence operand window exceeds 2 GiB (token stride x max_seqlen too large)'),
+    ("lbfa_attn_fwd_varlen", dict(sq=(64, 15790320), B=65536, Hq=65536, Hkv=1),
+     'lbfa_attn_fwd_varlen: grid too large'),
+    ("lbfa_attn_fwd_varlen", dict(sk=(64, 15790336)),
+     'lbfa_attn_fwd_varlen: per-sequence operand window exceeds 2 GiB (token stride x max_seqlen too large)'),
+    ("lbfa_attn_fwd_varlen", dict(sk=(64, 15790320), B=65536, Hq=65536, Hkv=1),
+     'lbfa_attn_fwd_varlen: grid too large'),
+    ("lbfa_attn_fwd_varlen", dict(sv=(64, 7895160)),
+     'lbfa_attn_fwd_varlen: per-sequence operand window exceeds 2 GiB (token stride x max_seqlen too large)'),
+    ("lbfa_attn_fwd_varlen", dict(sv=(64, 7895152), B=65536, Hq=65536, Hkv=1),
+     'lbfa_attn_fwd_varlen: grid too large'),
+    ("lbfa_attn_fwd_varlen", dict(B=65536, Hq=65536, Hkv=1),
+     'lbfa_attn_fwd_varlen: grid too large'),
+]
+
+
+# value of every workspace-size function on a grid of shapes, invalid ones (-> 0) included: (arguments, bytes)
+WORKSPACE_SIZES = {
+    "lbfa_mean_seq_workspace_bytes": [
+        ((1, 2, 8, 64), 1024),
+        ((2, 4, 300, 128), 16384),
+        ((1, 2, 20000, 64), 20480),
+        ((3, 2, 70000, 128), 423936),
+        ((1, 2, 8, 40), 640),
+        ((0, 2, 8, 64), 0),
+        ((1, 2, 8, 0), 0),
+    ],
+    "lbfa_v_fp8_bytes": [
+        ((1, 2, 8, 64), 8704),
+        ((2, 4, 300, 128), 331776),
+        ((1, 2, 20000, 64), 2564608),
+        ((3, 2, 70000, 128), 53775360),
+        ((1, 2, 8, 40), 5440),
+        ((0, 2, 8, 64), 0),
+        ((1, 2, 8, 0), 0),
+    ],
+    "lbfa_forward_workspace_bytes_dt": [
+        ((2, 8, 2, 300, 1000, 40, 0, 0, 0, 0), 264960),
+        ((2, 8, 2, 300, 1000, 40, 0, 0, 1, 1), 264960),
+        ((2, 8, 2, 300, 1000, 40, 0, 1, 1, 0), 529152),
+        ((2, 8, 2, 300, 1000, 40, 0, 1, 0, 1), 529152),
+        ((2, 8, 2, 300, 1000, 40, 1, 0, 0, 0), 776960),
+        ((2, 8, 2, 300, 1000, 40, 1, 0, 1, 1), 776960),
+        ((2, 8, 2, 300, 1000, 40, 1, 1, 1, 0), 529152),
+        ((2, 8, 2, 300, 1000, 40, 1, 1, 0, 1), 529152),
+        ((1, 4, 4, 128, 20000, 40, 0, 0, 0, 0), 5166592),
+        ((1, 4, 4, 128, 20000, 40, 0, 0, 1, 1), 5166592),
+        ((1, 4, 4, 128, 20000, 40, 0, 1, 1, 0), 10296832),
+        ((1, 4, 4, 128, 20000, 40, 0, 1, 0, 1), 10296832),
+        ((1, 4, 4, 128, 20000, 40, 1, 0, 0, 0), 15406592),
+        ((1, 4, 4, 128, 20000, 40, 1, 0, 1, 1), 15406592),
+        ((1, 4, 4, 128, 20000, 40, 1, 1, 1, 0), 10296832),
+        ((1, 4, 4, 128, 20000, 40, 1, 1, 0, 1), 10296832),
+        ((2, 8, 2, 300, 1000, 64, 0, 0, 0, 0), 264960),
+        ((2, 8, 2, 300, 1000, 64, 0, 0, 1, 1), 264960),
+        ((2, 8, 2, 300, 1000, 64, 0, 1, 1, 0), 529152),
+        ((2, 8, 2, 300, 1000, 64, 0, 1, 0, 1), 529152),
+        ((2, 8, 2, 300, 1000, 64, 1, 0, 0, 0), 776960),
+        ((2, 8, 2, 300, 1000, 64, 1, 0, 1, 1), 776960),
+        ((2, 8, 2, 300, 1000, 64, 1, 1, 1, 0), 529152),
+        ((2, 8, 2, 300, 1000, 64, 1, 1, 0, 1), 529152),
+        ((1, 4, 4, 128, 20000, 64, 0, 0, 0, 0), 5166592),
+        ((1, 4, 4, 128, 20000, 64, 0, 0, 1, 1), 5166592),
+        ((1, 4, 4, 128, 20000, 64, 0, 1, 1, 0), 10296832),
+        ((1, 4, 4, 128, 20000, 64, 0, 1, 0, 1), 10296832),
+        ((1, 4, 4, 128, 20000, 64, 1, 0, 0, 0), 15406592),
+        ((1, 4, 4, 128, 20000, 64, 1, 0, 1, 1), 15406592),
+        ((1, 4, 4, 128, 20000, 64, 1, 1, 1, 0), 10296832),
+        ((1, 4, 4, 128, 20000, 64, 1, 1, 0, 1), 10296832),
+        ((2, 8, 2, 300, 1000, 96, 0, 0, 0, 0), 529664),
+        ((2, 8, 2, 300, 1000, 96, 0, 0, 1, 1), 529664),
+        ((2, 8, 2, 300, 1000, 96, 0, 1, 1, 0), 1058048),
+        ((2, 8, 2, 300, 1000, 96, 0, 1, 0, 1), 1058048),
+        ((2, 8, 2, 300, 1000, 96, 1, 0, 0, 0), 1553664),
+        ((2, 8, 2, 300, 1000, 96, 1, 0, 1, 1), 1553664),
+        ((2, 8, 2, 300, 1000, 96, 1, 1, 1, 0), 1058048),
+        ((2, 8, 2, 300, 1000, 96, 1, 1, 0, 1), 1058048),
+        ((1, 4, 4, 128, 20000, 96, 0, 0, 0, 0), 10328064),
+        ((1, 4, 4, 128, 20000, 96, 0, 0, 1, 1), 10328064),
+        ((1, 4, 4, 128, 20000, 96, 0, 1, 1, 0), 20588544),
+        ((1, 4, 4, 128, 20000, 96, 0, 1, 0, 1), 20588544),
+        ((1, 4, 4, 128, 20000, 96, 1, 0, 0, 0), 30808064),
+        ((1, 4, 4, 128, 20000, 96, 1, 0, 1, 1), 30808064),
+        ((1, 4, 4, 128, 20000, 96, 1, 1, 1, 0), 20588544),
+        ((1, 4, 4, 128, 20000, 96, 1, 1, 0, 1), 20588544),
+        ((2, 8, 2, 300, 1000, 128, 0, 0, 0, 0), 529664),
+        ((2, 8, 2, 300, 1000, 128, 0, 0, 1, 1), 529664),
+        ((2, 8, 2, 300, 1000, 128, 0, 1, 1, 0), 1058048),
+        ((2, 8, 2, 300, 1000, 128, 0, 1, 0, 1), 1058048),
+        ((2, 8, 2, 300, 1000, 128, 1, 0, 0, 0), 1553664),
+        ((2, 8, 2, 300, 1000, 128, 1, 0, 1, 1), 1553664),
+        ((2, 8, 2, 300, 1000, 128, 1, 1, 1, 0), 1058048),
+        ((2, 8, 2, 300, 1000, 128, 1, 1, 0, 1), 1058048),
+        ((1, 4, 4, 128, 20000, 128, 0, 0, 0, 0), 10328064),
+        ((1, 4, 4, 128, 20000, 128, 0, 0, 1, 1), 10328064),
+        ((1, 4, 4, 128, 20000, 128, 0, 1, 1, 0), 20588544),
+        ((1, 4, 4, 128, 20000, 128, 0, 1, 0, 1), 20588544),
+        ((1, 4, 4, 128, 20000, 128, 1, 0, 0, 0), 30808064),
+        ((1, 4, 4, 128, 20000, 128, 1, 0, 1, 1), 30808064),
+        ((1, 4, 4, 128, 20000, 128, 1, 1, 1, 0), 20588544),
+        ((1, 4, 4, 128, 20000, 128, 1, 1, 0, 1), 20588544),
+        ((0, 2, 2, 8, 8, 64, 0, 0, 1, 0), 0),
+        ((1, 2, 2, 8, 8, 36, 0, 0, 1, 0), 0),
+        ((1, 2, 2, 8, 8, 136, 1, 0, 1, 0), 0),
+    ],
+    "lbfa_forward_workspace_bytes": [
+        ((2, 8, 2, 300, 1000, 40, 0, 1, 0), 776960),
+        ((2, 8, 2, 300, 1000, 40, 1, 1, 1), 529152),
+        ((1, 4, 4, 128, 20000, 40, 0, 1, 0), 15406592),
+        ((1, 4, 4, 128, 20000, 40, 1, 1, 1), 10296832),
+        ((2, 8, 2, 300, 1000, 64, 0, 1, 0), 776960),
+        ((2, 8, 2, 300, 1000, 64, 1, 1, 1), 529152),
+        ((1, 4, 4, 128, 20000, 64, 0, 1, 0), 15406592),
+        ((1, 4, 4, 128, 20000, 64, 1, 1, 1), 10296832),
+        ((2, 8, 2, 300, 1000, 96, 0, 1, 0), 1553664),
+        ((2, 8, 2, 300, 1000, 96, 1, 1, 1), 1058048),
+        ((1, 4, 4, 128, 20000, 96, 0, 1, 0), 30808064),
+        ((1, 4, 4, 128, 20000, 96, 1, 1, 1), 20588544),
+        ((2, 8, 2, 300, 1000, 128, 0, 1, 0), 1553664),
+        ((2, 8, 2, 300, 1000, 128, 1, 1, 1), 1058048),
+        ((1, 4, 4, 128, 20000, 128, 0, 1, 0), 30808064),
+        ((1, 4, 4, 128, 20000, 128, 1, 1, 1), 20588544),
+    ],
+}
+
+
+def test_single_fault_messages(lib):
+    check_table(lib, SINGLE_FAULT)
+
+
+def test_workspace_sizes_pinned(lib):
+    for fn, rows in WORKSPACE_SIZES.items():
+        for args, size in rows:
+            assert getattr(lib, fn)(*args) == size, (fn, args)
