@@ -230,6 +230,15 @@ int lbfa_sdpa_fwd(const void* q, const void* k, const void* v, int dtype, void* 
  *          correction taken out of the LSE is the forward's own, bit for bit: the pre-pass forms dtype(q . km) in the
  *          forward kernels' fp32 order (one dtype ulp of it would move a whole row of P by ulp * sm_scale * log2(e)).
  *          Per-element bound: tests/bwd_reference.py `grad_bound`.
+ *          Long rows: P and dS are rounded to the dtype before the gradient MFMAs, and most P of a long diffuse row lie below
+ *          the smallest normal fp16 (2^-14; 99.5 % of them at 131072 N(0,1) keys).  The conversion and the MFMA keep fp16
+ *          subnormals (tests/test_gpu_backward_long.py::test_mfma_keeps_fp16_subnormals), so such a P carries an absolute
+ *          error of at most 2^-25, not its whole value, and fp16 gradient accuracy degrades slowly with row length: measured
+ *          rel. L2 error against the float64 restatement at 131072 N(0,1) keys 3.2e-4 ... 3.6e-4 for dq / dk and 1.4e-3 for dv
+ *          (non-causal; 2.9e-4 causal), 2.8e-4 ... 3.3e-4 on peaky rows at 65537 and 131072 keys; bf16 2.2e-3 ... 2.6e-3 at every
+ *          length tested (its rounding of P and dS dominates).
+ *   window: none.  Unlike the forward entry points the backward addresses every operand with 64-bit offsets, so no operand
+ *          has a per-(batch, head) 2 GiB window: strides times lengths may exceed it (only the grid sizes are limited).
  */
 size_t lbfa_backward_workspace_bytes(int B, int Hq, int Hkv, int Sq, int Sk, int D, int q_qmax, int smooth_k);
 int lbfa_backward(const void* q, const void* k, const void* v, const void* o, const void* dout, int dtype, const float* lse,

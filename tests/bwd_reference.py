@@ -18,6 +18,8 @@ LOG2E = 1.44269504
 U32 = 2.0 ** -24                                  # fp32 unit roundoff (round to nearest even)
 U_DT = {"fp16": 2.0 ** -11, "bf16": 2.0 ** -8}    # unit roundoff of the input dtype
 TINY = {"fp16": 2.0 ** -14, "bf16": 2.0 ** -126}  # smallest normal number of the input dtype
+HALF_SUB = {"fp16": 2.0 ** -25, "bf16": 2.0 ** -134}  # half a step of its subnormal grid
+BLK = 64                                          # rows of a dQ workgroup / keys of a dK / dV workgroup
 EXP2_REL = 2.0 ** -23                             # __builtin_amdgcn_exp2f = v_exp_f32: 1 ulp (see grad_bound)
 LOG2E_LIT = abs(LOG2E - 1.0 / np.log(2.0)) / (1.0 / np.log(2.0))  # the literal 1.44269504 against log2(e)
 SAFETY = 2.0                                      # see grad_bound
@@ -27,57 +29,106 @@ def _rep(x, g):
     return np.repeat(x, g, axis=1) if g > 1 else x
 
 
-def _mask(Sq, Sk, is_causal):
-    if not is_causal:
-        return np.ones((Sq, Sk), bool)
-    return np.arange(Sk)[None, :] <= np.arange(Sq)[:, None]
+def _block_rows(blocks, S):
+    """absolute rows of the 64-row blocks `blocks` (ascending; None: every row) of a sequence of S rows - the dQ workgroup's query
+    rows or the dK / dV workgroup's keys (oracle.block_rows with 64-row blocks)"""
+    if blocks is None:
+        return np.arange(S)
+    return orc.block_rows(blocks, S, BLK) if len(blocks) else np.zeros(0, np.int64)
+
+
+def _all_blocks(S):
+    return [[b] for b in range(-(-S // BLK))]
+
+
+def prepare_p(q, k, lse, *, sm_scale, is_causal=False, dtype="fp16", q_qmax=0, k_qmax=0, smooth_k=False, km=None):
+    """What P needs of the whole tensors, O(S D): the codes and scales of `oracle.per_block_int8` over the whole tensor, the
+    correction fwd_corr and lse2 of every row (q_qmax = k_qmax = 0: the float64 q, shifted k and corrected natural-log LSE).
+    -> the context `p_panel` takes."""
+    B, Hq, Sq, D = q.shape
+    Hkv, Sk = k.shape[1], k.shape[2]
+    g = Hq // Hkv
+    c = dict(g=g, causal=is_causal, quant=q_qmax != 0, sm=sm_scale, D=D, Sq=Sq, Sk=Sk)
+    if q_qmax == 0:
+        qd = q.astype(np.float64)
+        c["qd"] = qd
+        c["kk"] = k.astype(np.float64) if km is None else k.astype(np.float64) - km.astype(np.float64)
+        corr = np.zeros((B, Hq, Sq)) if km is None else np.einsum("bhsd,bhtd->bhs", qd, _rep(km.astype(np.float64), g), optimize=True)
+        c["lsec"] = lse.astype(np.float64) - corr * sm_scale
+        c["lse2"] = lse.astype(np.float64) * LOG2E
+        c["aq"], c["ak"] = np.abs(qd), np.abs(k.astype(np.float64))
+        return c
+    kmq = orc.mean_seq(k, dtype) if smooth_k else None
+    q8, qs, k8, ks = orc.per_block_int8(q, k, kmq, sm_scale, dtype, q_qmax=float(q_qmax), k_qmax=float(k_qmax), amax_floor=1e-7)
+    corr = fwd_corr(q, _rep(kmq, g), dtype) if smooth_k else np.zeros((B, Hq, Sq))
+    return quantised_context(q8, qs, k8, ks, corr, lse, sm_scale, is_causal)
+
+
+def quantised_context(q8, qs, k8, ks, corr, lse, sm_scale, is_causal):
+    """the context of `p_panel` from codes [B, H, S, D], scales [B, H, blocks], the correction dtype(q . km) [B, Hq, Sq] and the
+    operator's natural-log LSE [B, Hq, Sq]"""
+    Sq, Sk = q8.shape[2], k8.shape[2]
+    c = dict(g=q8.shape[1] // k8.shape[1], causal=is_causal, quant=True, sm=sm_scale, D=q8.shape[3], Sq=Sq, Sk=Sk, q8=q8, k8=k8)
+    c["qsr"] = np.repeat(qs.astype(np.float64), 128, axis=2)[:, :, :Sq]
+    c["ksr"] = np.repeat(ks.astype(np.float64), 64, axis=2)[:, :, :Sk]
+    c["corrsm"] = corr.astype(np.float64) * sm_scale
+    c["lse2"] = (lse.astype(np.float64) - c["corrsm"]) * LOG2E
+    return c
+
+
+def p_panel(c, b, hk, rows, cols, return_arg_err=False):
+    """P [g, rows, cols] float64 of the g query heads of kv head (b, hk) at the absolute query rows `rows` and keys `cols`
+    (causal: key <= row, absolute), and on request the bound on the kernel's exponent-argument error (grad_bound)"""
+    g = c["g"]
+    hs = slice(hk * g, (hk + 1) * g)
+    mask = (cols[None, :] <= rows[:, None]) if c["causal"] else np.ones((len(rows), len(cols)), bool)
+    if not c["quant"]:
+        # natural-log domain: the forward multiplies by and divides by the same log2(e) literal, which cancels
+        qd, kk = c["qd"][b, hs][:, rows], c["kk"][b, hk][cols]
+        s = np.matmul(qd, kk.T) * c["sm"]
+        with np.errstate(invalid="ignore", over="ignore"):
+            p = np.where(mask, np.exp(s - c["lsec"][b, hs][:, rows][..., None]), 0.0)
+        if not return_arg_err:
+            return p
+        # the kernel: a = fp32 MFMA sum of the D exact 16-bit products, fl(a * fl(sm_scale log2e)) - fl(lse * fl(log2e))
+        sabs = np.matmul(c["aq"][b, hs][:, rows], c["ak"][b, hk][cols].T)
+        s2, lse2 = s * LOG2E, c["lse2"][b, hs][:, rows][..., None]
+        e = (U32 * (2 * np.abs(s2) + np.abs(s2 - lse2) + 3 * np.abs(lse2))
+             + LOG2E_LIT * (np.abs(s2) + np.abs(lse2)) + _gamma(c["D"]) * sabs * c["sm"] * LOG2E * (1 + 3 * U32))
+        return p, np.where(mask, e, 0.0)
+    si = np.matmul(c["q8"][b, hs][:, rows].astype(np.float64), c["k8"][b, hk][cols].astype(np.float64).T)
+    s2 = si * c["qsr"][b, hs][:, rows][..., None] * c["ksr"][b, hk][cols][None, None, :]
+    lse2 = c["lse2"][b, hs][:, rows]
+    with np.errstate(over="ignore"):  # masked scores may lie far above the LSE
+        p = np.where(mask, np.exp2(s2 - lse2[..., None]), 0.0)
+    if not return_arg_err:
+        return p
+    return p, np.where(mask, quantised_arg_err(s2, lse2, c["corrsm"][b, hs][:, rows]), 0.0)
 
 
 def recompute_p(q, k, lse, *, sm_scale, is_causal=False, dtype="fp16", q_qmax=0, k_qmax=0, smooth_k=False, km=None,
                 return_arg_err=False):
-    """P [B, Hq, Sq, Sk] float64 from the forward's scores and its natural-log LSE [B, Hq, Sq].
+    """P [B, Hq, Sq, Sk] float64 from the forward's scores and its natural-log LSE [B, Hq, Sq] (p_panel over all rows and keys).
 
     q_qmax = k_qmax = 0: un-quantised scores q.k * sm_scale (lbfa_sdpa_fwd), P = exp(s - lse).  `km` ([B, Hkv, 1, D]) then shifts the keys as
     smooth-K does, with the exact correction q.km taken out of the LSE (to check the invariance in float64).
     q_qmax in {127, 7}: the int8 / int4-range codes of `oracle.per_block_int8` (km = the oracle's mean when smooth_k) and the
     storage-dtype-rounded correction q.km of src/core.py:294-304, as the forward adds it to the LSE.
     return_arg_err: also the bound on the kernel's error in the exponent argument s2 - lse2 (binades, see grad_bound)."""
-    B, Hq, Sq, D = q.shape
+    B, Hq, Sq, _ = q.shape
     Hkv, Sk = k.shape[1], k.shape[2]
     g = Hq // Hkv
-    qd = q.astype(np.float64)
-    mask = _mask(Sq, Sk, is_causal)
-    if q_qmax == 0:
-        # natural-log domain: the forward multiplies by and divides by the same log2(e) literal, which cancels
-        kk = k.astype(np.float64) if km is None else k.astype(np.float64) - km.astype(np.float64)
-        s = np.einsum("bhsd,bhtd->bhst", qd, _rep(kk, g), optimize=True) * sm_scale
-        corr = np.zeros((B, Hq, Sq)) if km is None else np.einsum("bhsd,bhtd->bhs", qd, _rep(km.astype(np.float64), g), optimize=True)
-        lsec = lse.astype(np.float64) - corr * sm_scale
-        with np.errstate(invalid="ignore"):
-            p = np.where(mask, np.exp(s - lsec[..., None]), 0.0)
-        if not return_arg_err:
-            return p
-        # the kernel: a = fp32 MFMA sum of the D exact 16-bit products, fl(a * fl(sm_scale log2e)) - fl(lse * fl(log2e))
-        sabs = np.einsum("bhsd,bhtd->bhst", np.abs(qd), _rep(np.abs(k.astype(np.float64)), g), optimize=True)
-        s2, lse2 = s * LOG2E, lse.astype(np.float64) * LOG2E
-        e = (U32 * (2 * np.abs(s2) + np.abs(s2 - lse2[..., None]) + 3 * np.abs(lse2)[..., None])
-             + LOG2E_LIT * (np.abs(s2) + np.abs(lse2)[..., None]) + _gamma(D) * sabs * sm_scale * LOG2E * (1 + 3 * U32))
-        return p, np.where(mask, e, 0.0)
-    else:
-        kmq = orc.mean_seq(k, dtype) if smooth_k else None
-        q8, qs, k8, ks = orc.per_block_int8(q, k, kmq, sm_scale, dtype, q_qmax=float(q_qmax), k_qmax=float(k_qmax),
-                                            amax_floor=1e-7)
-        si = np.einsum("bhsd,bhtd->bhst", q8.astype(np.float64), _rep(k8.astype(np.float64), g), optimize=True)
-        qsr = np.repeat(qs.astype(np.float64), 128, axis=2)[:, :, :Sq]
-        ksr = np.repeat(ks.astype(np.float64), 64, axis=2)[:, :, :Sk]
-        s2 = si * qsr[..., :, None] * _rep(ksr, g)[..., None, :]
-        corr = fwd_corr(q, _rep(kmq, g), dtype) if smooth_k else np.zeros((B, Hq, Sq))
-    lse2 = (lse.astype(np.float64) - corr * sm_scale) * LOG2E
-    with np.errstate(over="ignore"):  # masked scores may lie far above the LSE
-        p = np.where(mask, np.exp2(s2 - lse2[..., None]), 0.0)
-    if not return_arg_err:
-        return p
-    return p, np.where(mask, quantised_arg_err(s2, lse2, corr * sm_scale), 0.0)
+    c = prepare_p(q, k, lse, sm_scale=sm_scale, is_causal=is_causal, dtype=dtype, q_qmax=q_qmax, k_qmax=k_qmax, smooth_k=smooth_k, km=km)
+    p, e = np.zeros((B, Hq, Sq, Sk)), (np.zeros((B, Hq, Sq, Sk)) if return_arg_err else None)
+    rows, cols = np.arange(Sq), np.arange(Sk)
+    for b in range(B):
+        for hk in range(Hkv):
+            r = p_panel(c, b, hk, rows, cols, return_arg_err)
+            if return_arg_err:
+                p[b, hk * g:(hk + 1) * g], e[b, hk * g:(hk + 1) * g] = r
+            else:
+                p[b, hk * g:(hk + 1) * g] = r
+    return (p, e) if return_arg_err else p
 
 
 def fwd_corr(q, km, dtype):
@@ -115,29 +166,135 @@ def _gamma(n):
 
 
 def _round_err(x, e, dtype):
-    """bound on the rounding to `dtype` of a kernel value within e of the exact |x|: relative u, and the whole value where it
-    may be subnormal (a round to the subnormal grid, a flush to zero: either is at most the value itself)"""
+    """bound on the rounding to `dtype` of a kernel value within e of the exact |x|: relative u, and below the smallest normal
+    half a step of the subnormal grid (the 16-bit conversion and the MFMA keep subnormals: grad_bound), and never more than
+    the value itself (below half a step it rounds to zero; an exact zero, a masked P, stays zero)"""
     hi = x + e
-    return U_DT[dtype] * hi + np.where(x - e < TINY[dtype], np.minimum(hi, TINY[dtype]), 0.0)
+    return np.minimum(hi, np.maximum(U_DT[dtype] * hi, HALF_SUB[dtype]))
+
+
+def sampled_from_p(p_fn, q, k, v, o, do, *, sm_scale, dtype="fp16", dlse=None, q_blocks=None, k_blocks=None, return_bound=False,
+                   workers=1):
+    """The gradients on sampled 64-row blocks, in O(S D) + O(64 S) memory per head: dq (and its bound) on the rows of the query
+    blocks `q_blocks` - P rows against all keys - and dk, dv (and their bounds) on the rows of the key blocks `k_blocks` - P
+    columns against all queries of the kv head's whole group.  None: every block (the full gradients), [] : none.
+    `p_fn(b, hk, rows, cols)` gives P [g, rows, cols] (return_bound: and the argument bound) - p_panel.  delta is formed for
+    all rows from o and do.  One 64-row block at a time, so a block's result does not depend on which others are asked for
+    (`workers`: that many blocks at a time, on threads).
+    -> dict(dq, dk, dv [B, H, sampled rows, D], rows_q, rows_k) and, with return_bound, bq, bk, bv (derivation: grad_bound)."""
+    B, Hq, Sq, D = q.shape
+    Hkv, Sk = k.shape[1], k.shape[2]
+    g = Hq // Hkv
+    qd, kd, vd, od, dod = (x.astype(np.float64) for x in (q, k, v, o, do))
+    delta = np.sum(dod * od, axis=-1)
+    adl = np.zeros((B, Hq, Sq)) if dlse is None else np.abs(dlse.astype(np.float64))
+    if dlse is not None:
+        delta = delta - dlse.astype(np.float64)
+    if return_bound:
+        aq, ak, av, ado = (np.abs(x) for x in (qd, kd, vd, dod))
+        edelta = _gamma(D + 1) * (np.sum(ado * np.abs(od), axis=-1) + adl)
+    qbl = _all_blocks(Sq) if q_blocks is None else [[int(x)] for x in q_blocks]
+    kbl = _all_blocks(Sk) if k_blocks is None else [[int(x)] for x in k_blocks]
+    rows_q = np.concatenate([_block_rows(x, Sq) for x in qbl]) if qbl else np.zeros(0, np.int64)
+    rows_k = np.concatenate([_block_rows(x, Sk) for x in kbl]) if kbl else np.zeros(0, np.int64)
+    res = dict(rows_q=rows_q, rows_k=rows_k, dq=np.zeros((B, Hq, len(rows_q), D)), dk=np.zeros((B, Hkv, len(rows_k), D)),
+               dv=np.zeros((B, Hkv, len(rows_k), v.shape[-1])))
+    if return_bound:
+        res.update(bq=np.zeros_like(res["dq"]), bk=np.zeros_like(res["dk"]), bv=np.zeros_like(res["dv"]))
+    all_q, all_k = np.arange(Sq), np.arange(Sk)
+
+    def panel(b, hk, rows, cols):
+        """P, dS [g, rows, cols] and, for the bound, the errors of P and dS after their rounding to the dtype and the magnitudes
+        the fp32 sums run over"""
+        hs = slice(hk * g, (hk + 1) * g)
+        p = p_fn(b, hk, rows, cols)
+        if return_bound:
+            p, arg_err = p
+        dor = dod[b, hs][:, rows]
+        dp = np.matmul(dor, vd[b, hk][cols].T)
+        tt = dp - delta[b, hs][:, rows][..., None]
+        ds = p * tt
+        if not return_bound:
+            return p, ds, None
+        # P before (eP) and after (ePr) its rounding to the dtype
+        with np.errstate(over="ignore"):
+            rho = np.exp2(arg_err) * (1 + EXP2_REL) - 1
+        eP = p * rho + np.minimum(p * (1 + rho), TINY["bf16"])
+        ePr = eP + _round_err(p, eP, dtype)
+        t = np.abs(tt)
+        et = (_gamma(D) * np.matmul(ado[b, hs][:, rows], av[b, hk][cols].T)
+              + edelta[b, hs][:, rows][..., None])
+        et = et * (1 + U32) + U32 * t
+        ads = p * t
+        eds = eP * (t + et) + p * et + U32 * (p + eP) * (t + et)
+        edsr = eds + _round_err(ads, eds, dtype)
+        return p, ds, (ePr, p + ePr, edsr, ads + edsr)
+
+    def store(x, e):
+        return SAFETY * (e + _round_err(np.abs(x), e, dtype))
+
+    def dq_block(b, hk, rows, sl):  # dq: sum over the keys (Sk terms), times fl(sm_scale)
+        hs = slice(hk * g, (hk + 1) * g)
+        p, ds, eb = panel(b, hk, rows, all_k)
+        dq = sm_scale * np.matmul(ds, kd[b, hk])
+        res["dq"][b, hs, sl] = dq
+        if return_bound:
+            _, _, edsr, ds_mag = eb
+            eq = sm_scale * (np.matmul(edsr, ak[b, hk])
+                             + (_gamma(Sk) + 2 * U32) * np.matmul(ds_mag, ak[b, hk]))
+            res["bq"][b, hs, sl] = store(dq, eq)
+
+    def dkv_block(b, hk, cols, sl):  # dk / dv: sum over the group's query rows (g Sq terms); dk times fl(sm_scale)
+        hs = slice(hk * g, (hk + 1) * g)
+        p, ds, eb = panel(b, hk, all_q, cols)
+        dk = sm_scale * np.matmul(ds.transpose(0, 2, 1), qd[b, hs]).sum(axis=0)
+        dv = np.matmul(p.transpose(0, 2, 1), dod[b, hs]).sum(axis=0)
+        res["dk"][b, hk, sl], res["dv"][b, hk, sl] = dk, dv
+        if return_bound:
+            ePr, pr_mag, edsr, ds_mag = eb
+            ev = (np.matmul(ePr.transpose(0, 2, 1), ado[b, hs])
+                  + _gamma(g * Sq) * np.matmul(pr_mag.transpose(0, 2, 1), ado[b, hs])).sum(axis=0)
+            ek = sm_scale * (np.matmul(edsr.transpose(0, 2, 1), aq[b, hs])
+                             + (_gamma(g * Sq) + 2 * U32) * np.matmul(ds_mag.transpose(0, 2, 1), aq[b, hs])).sum(axis=0)
+            res["bk"][b, hk, sl], res["bv"][b, hk, sl] = store(dk, ek), store(dv, ev)
+
+    tasks = []
+    for b in range(B):
+        for hk in range(Hkv):
+            for fn, bl, S in ((dq_block, qbl, Sq), (dkv_block, kbl, Sk)):
+                at = 0
+                for blk in bl:
+                    rows = _block_rows(blk, S)
+                    tasks.append((fn, b, hk, rows, slice(at, at + len(rows))))
+                    at += len(rows)
+    limits = None
+    if workers > 1:  # each thread's BLAS must then stay single-threaded, or the threads fight over the cores
+        try:
+            from threadpoolctl import threadpool_limits as limits
+        except ImportError:
+            workers = 1
+    if workers > 1:  # blocks are independent and write disjoint rows
+        from concurrent.futures import ThreadPoolExecutor
+        with limits(limits=1, user_api="blas"), ThreadPoolExecutor(workers) as ex:
+            list(ex.map(lambda t: t[0](*t[1:]), tasks))
+    else:
+        for t in tasks:
+            t[0](*t[1:])
+    return res
+
+
+def _slicer(p, arg_err, g):
+    """p_fn of sampled_from_p for a given full P [B, Hq, Sq, Sk] (and argument bound)"""
+    def p_fn(b, hk, rows, cols):
+        cut = lambda x: x[b, hk * g:(hk + 1) * g][:, rows[:, None], cols[None, :]]
+        return cut(p) if arg_err is None else (cut(p), cut(arg_err))
+    return p_fn
 
 
 def grads_from_p(p, q, k, v, o, do, *, sm_scale, dlse=None):
-    """(dq, dk, dv) float64 for a given P [B, Hq, Sq, Sk]"""
-    Hq, Hkv = q.shape[1], k.shape[1]
-    g = Hq // Hkv
-    qd, kd, vd, od, dod = (x.astype(np.float64) for x in (q, k, v, o, do))
-    dv_h = np.einsum("bhst,bhsd->bhtd", p, dod, optimize=True)
-    dp = np.einsum("bhsd,bhtd->bhst", dod, _rep(vd, g), optimize=True)
-    delta = np.sum(dod * od, axis=-1)
-    if dlse is not None:
-        delta = delta - dlse.astype(np.float64)
-    ds = p * (dp - delta[..., None])
-    dq = sm_scale * np.einsum("bhst,bhtd->bhsd", ds, _rep(kd, g), optimize=True)
-    dk_h = sm_scale * np.einsum("bhst,bhsd->bhtd", ds, qd, optimize=True)
-    B, _, Sk, D = k.shape
-    dk = dk_h.reshape(B, Hkv, g, Sk, D).sum(axis=2)
-    dv = dv_h.reshape(B, Hkv, g, Sk, v.shape[-1]).sum(axis=2)
-    return dq, dk, dv
+    """(dq, dk, dv) float64 for a given P [B, Hq, Sq, Sk]: sampled_from_p with every block"""
+    r = sampled_from_p(_slicer(p, None, q.shape[1] // k.shape[1]), q, k, v, o, do, sm_scale=sm_scale, dlse=dlse)
+    return r["dq"], r["dk"], r["dv"]
 
 
 def grad_bound(p, arg_err, q, k, v, o, do, *, sm_scale, dtype="fp16", dlse=None):
@@ -157,12 +314,13 @@ def grad_bound(p, arg_err, q, k, v, o, do, *, sm_scale, dtype="fp16", dlse=None)
                 This grows with the scores: at |s2| ~ |lse2| ~ 2^14 binades (randint inputs, D = 128) it is ~2^-8 binades,
                 more than the fp16 rounding of P.
       P         fl(exp2(x)): v_exp_f32 is accurate to 1 ulp (AMD Instinct CDNA3 ISA reference guide, V_EXP_F32; the HIP math
-                library's exp2f, built on it, documents the same 1 ulp), so P_k = P 2^(+-arg_err) (1 +- 2^-23); a subnormal
-                result may be flushed (at most P itself).
-      P, dS     rounded once each to the input dtype (pack_pair: store_cvt) - relative u = 2^-11 (fp16) / 2^-8 (bf16).  Whether
-                the f16 / bf16 A / B inputs of v_mfma_f32_16x16x32_{f16,bf16} flush subnormals on gfx950 is not settled by
-                the ISA text at hand (it covers C / D and f32 A / B), so the flush is modelled: below the smallest normal the
-                error is the whole value (_round_err).
+                library's exp2f, built on it, documents the same 1 ulp), so P_k = P 2^(+-arg_err) (1 +- 2^-23); an fp32
+                subnormal result may be flushed (at most 2^-126).
+      P, dS     rounded once each to the input dtype (pack_pair: store_cvt) - relative u = 2^-11 (fp16) / 2^-8 (bf16), and
+                below the smallest normal half a step of the subnormal grid (2^-25 for fp16): neither the conversion nor the
+                f16 / bf16 A / B inputs of v_mfma_f32_16x16x32_{f16,bf16} flush subnormals on gfx950, which
+                test_gpu_backward_long.py::test_mfma_keeps_fp16_subnormals settles with P = 2^-15 .. 2^-17 exactly
+                (_round_err).
       dP, delta dP = fp32 MFMA sum over D: gamma_D sum_d |dO||V|; delta = fp32 fma chain over D, then - dLSE:
                 gamma_(D+1) (sum_d |dO||O| + |dLSE|).
       dS        fl(P_k fl(dP - delta)): the errors of P_k, dP and delta propagated, plus two fp32 roundings.
@@ -175,54 +333,25 @@ def grad_bound(p, arg_err, q, k, v, o, do, *, sm_scale, dtype="fp16", dlse=None)
     is tight there; and two inputs of the derivation are documented facts rather than derived from this code (the 1-ulp
     accuracy of v_exp_f32; that no unit on the path flushes or rounds other than as modelled).  The factor keeps an error
     in either from failing a correct kernel; test_bwd_bound_cpu.py shows every listed bug is still rejected with it."""
-    B, Hq, Sq, D = q.shape
-    Hkv, Sk = k.shape[1], k.shape[2]
-    g = Hq // Hkv
-    u = U_DT[dtype]
-    aq, ak, av, ao, ado = (np.abs(x.astype(np.float64)) for x in (q, k, v, o, do))
-    ak, av = _rep(ak, g), _rep(av, g)
-    # P before (eP) and after (ePr) its rounding to the dtype
-    with np.errstate(over="ignore"):
-        rho = np.exp2(arg_err) * (1 + EXP2_REL) - 1
-    eP = p * rho + np.minimum(p * (1 + rho), TINY["bf16"])
-    ePr = eP + _round_err(p, eP, dtype)
-    # dP - delta and dS
-    dp = np.einsum("bhsd,bhtd->bhst", do.astype(np.float64), _rep(v.astype(np.float64), g), optimize=True)
-    delta = np.sum(do.astype(np.float64) * o.astype(np.float64), axis=-1)
-    adl = np.zeros((B, Hq, Sq)) if dlse is None else np.abs(dlse.astype(np.float64))
-    if dlse is not None:
-        delta = delta - dlse.astype(np.float64)
-    t = np.abs(dp - delta[..., None])
-    et = (_gamma(D) * np.einsum("bhsd,bhtd->bhst", ado, av, optimize=True)
-          + (_gamma(D + 1) * (np.sum(ado * ao, axis=-1) + adl))[..., None])
-    et = et * (1 + U32) + U32 * t
-    ds = p * t
-    eds = eP * (t + et) + p * et + U32 * (p + eP) * (t + et)
-    edsr = eds + _round_err(ds, eds, dtype)
+    r = sampled_from_p(_slicer(p, arg_err, q.shape[1] // k.shape[1]), q, k, v, o, do, sm_scale=sm_scale, dtype=dtype, dlse=dlse,
+                       return_bound=True)
+    return r["bq"], r["bk"], r["bv"]
 
-    # outputs: sum |term error| + gamma_N sum |term|; dq / dk times fl(sm_scale)
-    pr_mag = p + ePr
-    ev = np.einsum("bhst,bhsd->bhtd", ePr, ado, optimize=True) + _gamma(g * Sq) * np.einsum("bhst,bhsd->bhtd", pr_mag, ado, optimize=True)
-    ds_mag = ds + edsr
-    ek = sm_scale * (np.einsum("bhst,bhsd->bhtd", edsr, aq, optimize=True)
-                     + (_gamma(g * Sq) + 2 * U32) * np.einsum("bhst,bhsd->bhtd", ds_mag, aq, optimize=True))
-    eq = sm_scale * (np.einsum("bhst,bhtd->bhsd", edsr, ak, optimize=True)
-                     + (_gamma(Sk) + 2 * U32) * np.einsum("bhst,bhtd->bhsd", ds_mag, ak, optimize=True))
-    ev = ev.reshape(B, Hkv, g, Sk, D).sum(axis=2)
-    ek = ek.reshape(B, Hkv, g, Sk, D).sum(axis=2)
-    dq, dk, dv = grads_from_p(p, q, k, v, o, do, sm_scale=sm_scale, dlse=dlse)
-    return tuple(SAFETY * (e + _round_err(np.abs(x), e, dtype)) for x, e in ((dq, eq), (dk, ek), (dv, ev)))
+
+def attention_backward_sampled(q, k, v, o, lse, do, *, sm_scale, is_causal=False, dtype="fp16", q_qmax=0, k_qmax=0, smooth_k=False,
+                               dlse=None, km=None, q_blocks=None, k_blocks=None, return_bound=False, workers=1):
+    """sampled_from_p with the contract's P (prepare_p / p_panel): dq on the 64-row query blocks `q_blocks`, dk / dv on the 64-key
+    blocks `k_blocks` (None: all), o and lse the operator's for ALL rows; memory O(S D) + O(64 S) per head."""
+    c = prepare_p(q, k, lse, sm_scale=sm_scale, is_causal=is_causal, dtype=dtype, q_qmax=q_qmax, k_qmax=k_qmax, smooth_k=smooth_k, km=km)
+    return sampled_from_p(lambda b, hk, rows, cols: p_panel(c, b, hk, rows, cols, return_bound), q, k, v, o, do, sm_scale=sm_scale,
+                          dtype=dtype, dlse=dlse, q_blocks=q_blocks, k_blocks=k_blocks, return_bound=return_bound, workers=workers)
 
 
 def attention_backward(q, k, v, o, lse, do, *, sm_scale, is_causal=False, dtype="fp16", q_qmax=0, k_qmax=0, smooth_k=False,
                        dlse=None, km=None, return_bound=False):
-    """(dq, dk, dv) float64 of the contract: P recomputed (recompute_p), then grads_from_p.  o and lse are the operator's.
+    """(dq, dk, dv) float64 of the contract: attention_backward_sampled with every block.  o and lse are the operator's.
     return_bound: (dq, dk, dv, bq, bk, bv), the b* the per-element bound of grad_bound (the largest deviation of a correct
     kernel from dq / dk / dv)."""
-    p = recompute_p(q, k, lse, sm_scale=sm_scale, is_causal=is_causal, dtype=dtype, q_qmax=q_qmax, k_qmax=k_qmax,
-                    smooth_k=smooth_k, km=km, return_arg_err=return_bound)
-    if not return_bound:
-        return grads_from_p(p, q, k, v, o, do, sm_scale=sm_scale, dlse=dlse)
-    p, e = p
-    return (grads_from_p(p, q, k, v, o, do, sm_scale=sm_scale, dlse=dlse)
-            + grad_bound(p, e, q, k, v, o, do, sm_scale=sm_scale, dtype=dtype, dlse=dlse))
+    r = attention_backward_sampled(q, k, v, o, lse, do, sm_scale=sm_scale, is_causal=is_causal, dtype=dtype, q_qmax=q_qmax,
+                                   k_qmax=k_qmax, smooth_k=smooth_k, dlse=dlse, km=km, return_bound=return_bound)
+    return tuple(r[x] for x in (("dq", "dk", "dv", "bq", "bk", "bv") if return_bound else ("dq", "dk", "dv")))

@@ -8,11 +8,14 @@ P and dS rounded to the dtype (orc.to_storage) before fp32 products summed over 
 dq / dk times fl(sm_scale), stores in the dtype.  Switches give what a correct kernel may do differently (sound: every one
 must pass the bound against the float64 reference) and plain bugs (sharp: each must be rejected on at least one case).
 For every bug the old per-tensor check (test_gpu_backward._assert_close) is run as well and its verdict printed:
-`BWDMUTANT <name> new: rejected on i/n cases, old: accepted on j/n`."""
+`BWDMUTANT <name> new: rejected on i/n cases, old: accepted on j/n`.
+The block-sampled form of the reference (attention_backward_sampled, what the long-sequence GPU tests use) gives the full
+form's gradients and bounds bit for bit on the sampled rows, and still rejects every listed bug on a sampling that holds the
+block the bug touches."""
 import numpy as np
 import pytest
 
-from bwd_reference import LOG2E, attention_backward, fwd_corr
+from bwd_reference import LOG2E, attention_backward, attention_backward_sampled, fwd_corr
 from oracle import lowbit_fa_oracle as orc
 
 F32 = np.float32
@@ -248,3 +251,47 @@ def test_bound_is_sharp(sharp_cases, mutant):
           "(per case new/old, R rejected, a accepted: " +
           ", ".join(f"{'R' if r else 'a'}/{'a' if a else 'R'}" for r, a in zip(rejected, old)) + ")")
     assert any(rejected), f"{mutant}: no case rejects it"
+
+
+# ---- the block-sampled form ----
+def _sampled(c, data, q_blocks, k_blocks):
+    q, k, v, o, lse, do, dlse = data
+    return attention_backward_sampled(q, k, v, o, lse, do, sm_scale=c["sm"], is_causal=c["causal"], dtype=c["dtype"], q_qmax=c["qmax"],
+                                      k_qmax=c["kmax"], smooth_k=c["smooth"] and c["qmax"] != 0, dlse=dlse, q_blocks=q_blocks,
+                                      k_blocks=k_blocks, return_bound=True)
+
+
+def _sampling(c):
+    """query blocks 0, 1 (rows 64..127: the second half of the first quantiser block) and the last; key blocks 0 and the last"""
+    nq, nk = -(-c["Sq"] // 64), -(-c["Sk"] // 64)
+    return sorted({0, min(1, nq - 1), nq - 1}), sorted({0, nk - 1})
+
+
+@pytest.mark.parametrize("ci", range(len(SOUND)))
+def test_sampled_equals_full_on_the_sampled_rows(ci):
+    """EQUAL, not close: the full form is the sampled form with every block, one 64-row block at a time, so a block sees the
+    same float64 operations on the same shapes whichever other blocks are asked for."""
+    c, data, ref = _case(SOUND[ci])
+    nq, nk = -(-c["Sq"] // 64), -(-c["Sk"] // 64)
+    qb, kb = [nq - 1], ([0, nk - 1] if nk > 2 else [nk - 1])  # the ragged last blocks among them
+    r = _sampled(c, data, qb, kb)
+    assert len(r["rows_q"]) < c["Sq"] and len(r["rows_k"]) < c["Sk"] and r["rows_q"][-1] == c["Sq"] - 1 and r["rows_k"][-1] == c["Sk"] - 1
+    for i, (name, rows) in enumerate((("dq", "rows_q"), ("dk", "rows_k"), ("dv", "rows_k"))):
+        assert np.array_equal(r[name], ref[i][:, :, r[rows]]), name
+        assert np.array_equal(r["b" + name[1]], ref[3 + i][:, :, r[rows]]), "bound of " + name
+    assert _sampled(c, data, [], kb)["dq"].shape[2] == 0 and np.array_equal(_sampled(c, data, [], kb)["dk"], r["dk"])
+
+
+@pytest.mark.parametrize("mutant", MUTANTS)
+def test_sampled_bound_is_sharp(sharp_cases, mutant):
+    """every listed bug is still rejected when only the sampled blocks are compared (each bug touches query block 0, 1 or the
+    last, or key block 0 or the last, or every block)"""
+    rejected = []
+    for c, data, _ in sharp_cases:
+        qb, kb = _sampling(c)
+        r = _sampled(c, data, qb, kb)
+        got = _kernel(*data, c, var=mutant)
+        cut = (got[0][:, :, r["rows_q"]], got[1][:, :, r["rows_k"]], got[2][:, :, r["rows_k"]])
+        rejected.append(_worst(cut, (r["dq"], r["dk"], r["dv"], r["bq"], r["bk"], r["bv"])) > 1.0)
+    print(f"BWDMUTANT {mutant} sampled: rejected on {sum(rejected)}/{len(rejected)} cases")
+    assert any(rejected), f"{mutant}: no case rejects it on the sampled blocks"

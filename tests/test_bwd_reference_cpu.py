@@ -2,7 +2,7 @@
 import numpy as np
 import pytest
 
-from bwd_reference import attention_backward, grads_from_p, recompute_p
+from bwd_reference import attention_backward, attention_backward_sampled, grads_from_p, recompute_p
 
 torch = pytest.importorskip("torch")
 
@@ -96,3 +96,21 @@ def test_quantised_p_is_normalised_by_its_own_lse(oracle):
             lse = (lse.astype(np.float64) + (fwd_corr(q, km, "fp16") - c_orc) * 64 ** -0.5).astype(np.float32)
         p = recompute_p(q, k, lse, sm_scale=64 ** -0.5, is_causal=True, q_qmax=127, k_qmax=127, smooth_k=smooth)
         assert np.abs(p.sum(-1) - 1).max() <= 1e-5
+
+
+@pytest.mark.parametrize("causal,Hq,Hkv,Sq,Sk", [(False, 2, 2, 137, 150), (True, 4, 2, 145, 145), (False, 6, 2, 1, 129)])
+def test_sampled_blocks_equal_the_full_gradients(causal, Hq, Hkv, Sq, Sk):
+    """attention_backward_sampled on some 64-row blocks gives the rows of attention_backward bit for bit (the full form is the
+    sampled form with all blocks), and the causal mask of a sampled block uses its absolute rows: it matches autograd."""
+    q, k, v = _inputs(2, Hq, Hkv, Sq, Sk, 16, seed=Sq + Hq)
+    rng = np.random.default_rng(5)
+    do, dlse = rng.standard_normal(q.shape), rng.standard_normal(q.shape[:3])
+    sm = 0.3
+    o, lse, want = _autograd(q, k, v, do, dlse, causal, sm)
+    full = attention_backward(q, k, v, o, lse, do, sm_scale=sm, is_causal=causal, dlse=dlse)
+    qb, kb = [(Sq - 1) // 64], sorted({0, (Sk - 1) // 64})
+    r = attention_backward_sampled(q, k, v, o, lse, do, sm_scale=sm, is_causal=causal, dlse=dlse, q_blocks=qb, k_blocks=kb)
+    assert r["rows_q"][0] == 64 * qb[0] and r["rows_q"][-1] == Sq - 1 and r["rows_k"][0] == 0 and r["rows_k"][-1] == Sk - 1
+    for name, f, w, rows in zip(("dq", "dk", "dv"), full, want, (r["rows_q"], r["rows_k"], r["rows_k"])):
+        assert np.array_equal(r[name], f[:, :, rows]), name
+        assert np.abs(r[name] - w[:, :, rows]).max() <= 1e-10 * max(1.0, np.abs(w).max())

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 from bwd_reference import attention_backward
-from bwd_varlen_reference import varlen_backward, varlen_lse
+from bwd_varlen_reference import packed_codes, varlen_backward, varlen_lse
 from oracle import lowbit_fa_oracle as orc
 
 torch = pytest.importorskip("torch")
@@ -96,3 +96,38 @@ def test_packing_matches_torch_autograd_of_float64_attention(causal):
     got = varlen_backward(q, k, v, o, lse, do, cu_q, cu_k, is_causal=causal, dlse=dlse, p_fn=p_fn)
     for g, w in zip(got, want):
         np.testing.assert_allclose(g, w, rtol=1e-10, atol=1e-12)
+
+
+@pytest.mark.parametrize("D,smooth_k,qmax", [(64, True, 127), (80, True, 7), (128, False, 127)])
+def test_packed_codes_are_the_oracles(D, smooth_k, qmax):
+    """packed_codes (no attention, linear in the lengths) gives the intermediates of oracle.lowbit_fa_varlen bit for bit"""
+    lens_q, lens_k = [70, 0, 129, 5, 1], [3, 40, 129, 0, 200]
+    q, k, v, cu_q, cu_k = orc.make_varlen_inputs(lens_q, lens_k, 4, 2, D, seed=D, k_bias=0.4)
+    _, want = orc.lowbit_fa_varlen(q, k, v, cu_q, cu_k, smooth_k=smooth_k, q_qmax=float(qmax), k_qmax=float(qmax), tail="neg_inf",
+                                   amax_floor=1e-7, return_intermediates=True)
+    got = packed_codes(q, k, cu_q, cu_k, dtype="fp16", sm_scale=D ** -0.5, smooth_k=smooth_k, q_qmax=qmax, k_qmax=qmax)
+    for name in ("q_i8", "k_i8", "q_scale", "k_scale"):
+        assert np.array_equal(got[name], want[name]), name
+    assert (got["km"] is None and want["km"] is None) if not smooth_k else np.array_equal(got["km"], want["km"])
+
+
+@pytest.mark.parametrize("causal", [False, True])
+def test_sampled_blocks_of_a_sequence_equal_the_full_packed_result(causal):
+    """`blocks` samples 64-row blocks of the named sequences: values and bounds equal the full result bit for bit on the tokens
+    the returned masks name, the other tokens of those sequences stay zero, the other sequences are computed completely."""
+    lens = [70, 300, 0, 131]
+    q, k, v, o, lse, do, cu_q, cu_k = _inputs(lens, lens, 4, 2, 64, 9, causal)
+    dlse = np.random.default_rng(6).standard_normal(lse.shape)
+    full = varlen_backward(q, k, v, o, lse, do, cu_q, cu_k, is_causal=causal, dlse=dlse, return_bound=True)
+    got = varlen_backward(q, k, v, o, lse, do, cu_q, cu_k, is_causal=causal, dlse=dlse, return_bound=True,
+                          blocks={1: ([1, 4], [0, 4]), 3: ([], None)})
+    mq, mk = got[6:]
+    want_q = np.ones(q.shape[0], bool)
+    want_q[cu_q[1]:cu_q[2]] = False
+    want_q[cu_q[1] + 64:cu_q[1] + 128] = want_q[cu_q[1] + 256:cu_q[2]] = True
+    want_q[cu_q[3]:cu_q[4]] = False
+    want_k = np.ones(k.shape[0], bool)
+    want_k[cu_k[1] + 64:cu_k[1] + 256] = False
+    assert np.array_equal(mq, want_q) and np.array_equal(mk, want_k)
+    for i, m in enumerate((mq, mk, mk, mq, mk, mk)):
+        assert np.array_equal(got[i][m], full[i][m]) and not got[i][~m].any(), i

@@ -290,12 +290,12 @@ def _torch_reference_head(q, k, v, o, lse, do, sm_scale, causal, return_bound=Fa
 
 def _torch_bound_head(ref, p, arg_err, q, k, v, o, do, sm_scale, dtype):
     """bwd_reference.grad_bound in torch float64 for one (b, h) (no GQA, no dLSE): [S, S] P and argument bound, [S, D] tensors"""
-    from bwd_reference import EXP2_REL, SAFETY, TINY, U32, U_DT, _gamma
-    u, tn = U_DT[dtype], TINY[dtype]
+    from bwd_reference import EXP2_REL, HALF_SUB, SAFETY, TINY, U32, U_DT, _gamma
+    u, half = U_DT[dtype], HALF_SUB[dtype]
 
-    def rerr(x, e):
+    def rerr(x, e):  # bwd_reference._round_err
         hi = x + e
-        return u * hi + torch.where(x - e < tn, torch.clamp(hi, max=tn), torch.zeros_like(hi))
+        return torch.minimum(hi, torch.clamp(u * hi, min=half))
 
     S, D = q.shape
     aq, ak, av, ao, ado = (t.double().abs() for t in (q, k, v, o, do))
