@@ -335,6 +335,64 @@ int lbfa_backward_varlen(const void* q, const void* k, const void* v, const void
                          const int64_t strides_dv[2], double sm_scale, int q_qmax, int k_qmax, int is_causal, int smooth_k,
                          void* stream);
 
+/*
+ * Int8 KV cache and decode attention for short queries (additive to ABI 200, LBFA_VERSION unchanged: look the symbols up).
+ *
+ * The cache of a batch, all tensors contiguous and caller-owned (capacity a multiple of 64, D in {64, 128}; other head dims are
+ * zero-padded by the caller - only the new tokens):
+ *   k_codes int8 [B, Hkv, capacity, D]      codes of K - km, one per byte (range 127 or 7)
+ *   k_scale fp32 [B, Hkv, capacity / 64]    one scale per 64 keys
+ *   v_cache fp16 [B, Hkv, capacity, D]      V as the attention kernels see it (`v.to(float16)`; a bf16 V is cast on append)
+ *   k_tail  [B, Hkv, 64, D] storage dtype   raw rows of the OPEN 64-key block (the one the next token falls into)
+ *   km      [B, Hkv, D] storage dtype       smooth-K mean, FIXED for the life of the cache, or NULL (no smoothing)
+ *   seqlens int32 [B] on the device         valid keys per sequence
+ *
+ * lbfa_kvcache_append adds the rows k_new / v_new [B, Hkv, T, D] (dtype, strides {batch, head, seq} in elements) of which
+ * sequence b takes the first new_lens[b] <= T (new_lens NULL: all T), at positions [seqlens[b], seqlens[b] + new_lens[b]).
+ * Afterwards every 64-key block those rows touch holds the codes and the scale lbfa_quant_per_block(dtype(K - km), blk = 64,
+ * k_qmax) produces for that block of the concatenated K, bit for bit (1e-7 floor included; the scale of the partial last block
+ * comes from the rows present): the open block is re-quantised from k_tail plus the new rows, and k_tail then holds the raw rows
+ * of the new open block.  seqlens is READ on the device and NOT advanced: the caller adds new_lens afterwards.  Rows that would
+ * pass the capacity are dropped.  Race-free and scheduling-independent for any T (one workgroup owns both ends of the range).
+ * km is an input: on the first append the caller fills it with lbfa_mean_seq (all sequences T rows: the mean the dense operators
+ * use, so the codes are theirs) or lbfa_kvcache_mean (ragged: storage dtype of the float64 mean over the new_lens[b] valid
+ * rows, zeros for an empty sequence).  A softmax row is invariant to any fixed shift of K; lbfa_decode corrects the LSE.
+ */
+int lbfa_kvcache_mean(const void* k_new, int dtype, const int32_t* new_lens, void* km, int B, int Hkv, int T, int D,
+                      const int64_t strides_k[3], void* stream);
+int lbfa_kvcache_append(const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
+                        int8_t* k_codes, float* k_scale, void* v_cache, void* k_tail, const int32_t* seqlens,
+                        int B, int Hkv, int T, int D, int capacity, const int64_t strides_k[3], const int64_t strides_v[3],
+                        int k_qmax, void* stream);
+
+/*
+ * lbfa_decode: O = softmax(dequant(Q K^T)) V of q [B, Hq, Sq, D] (fp16 / bf16, strides_q) over the cache, for
+ * M = Sq * (Hq / Hkv) <= 64 query rows per kv head (more: LBFA_EINVAL - such calls belong on the dense operator).
+ *   seqlens[b]    : valid keys of sequence b, the tokens just appended included; max_seqlen_k (1 .. capacity) is a host upper
+ *                   bound that sizes the grid, longer sequences are cut there.  seqlens[b] == 0: zeros and LSE -inf.
+ *   Q             : quantised inside the kernel, the Sq rows of one (batch, head) as one block with fp32(sm_scale * 1.44269504)
+ *                   formed in double: codes and scale bit-identical to lbfa_quant_per_block (blk = 128) on q.
+ *   arithmetic    : int8 MFMA scores x q_scale x k_scale, online softmax in base 2, P rounded to fp16, fp16 MFMA against
+ *                   v_cache, fp32 accumulation.  Keys >= seqlens[b] are masked with -inf.
+ *   is_causal     : bottom-right aligned - query i sees keys < seqlens[b] - Sq + 1 + i (a query that sees none: zeros, -inf).
+ *   num_splits    : key slices per sequence, cut at multiples of 64 keys (slice s = tiles [s * tps, (s + 1) * tps) of the
+ *                   sequence's ceil(len / 64), tps = ceil(tiles / num_splits)); 0 = lbfa_decode_num_splits(B, Hkv, max_seqlen_k):
+ *                   min(ceil(1024 / (B * Hkv)), tiles / 4, 256), at least 1.  One slice writes o directly (one launch); more
+ *                   write fp32 partials to the workspace and a second kernel adds them in one fixed order: no atomics, bitwise
+ *                   reproducible for a given num_splits.
+ *   o             : [B, Hq, Sq, D] in dtype, strides_o.  lse: NULL or [B, Hq, Sq] fp32 natural log, including the smooth-K
+ *                   correction dtype(q . km) * sm_scale as lbfa_forward defines it (km NULL: none).
+ *   workspace     : >= lbfa_decode_workspace_bytes(..., num_splits) bytes, 16-byte aligned (0 bytes / NULL with one slice).
+ *   No 2 GiB window: the cache is addressed with 64-bit offsets.  Every argument is checked before the first launch; the call
+ *   only enqueues on `stream`.
+ */
+int lbfa_decode_num_splits(int B, int Hkv, int max_seqlen_k);
+size_t lbfa_decode_workspace_bytes(int B, int Hq, int Hkv, int Sq, int D, int max_seqlen_k, int num_splits);
+int lbfa_decode(const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const void* v_cache, const void* km,
+                const int32_t* seqlens, void* o, float* lse, void* workspace, size_t workspace_bytes,
+                int B, int Hq, int Hkv, int Sq, int D, int capacity, int max_seqlen_k, int num_splits,
+                const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,5 +20,11 @@ from .core import (  # noqa: F401
     lowbit_fa_qk_int8_pv_fp8_cuda,
     lowbit_fa_qk_int4_pv_fp16_triton,
 )
+from .kvcache import (  # noqa: F401
+    # int8 KV cache + split-KV decode attention (no counterpart that works in the reference: SURVEY.md row 8)
+    LowbitKVCache,
+    lowbit_fa_decode,
+    sageattn_decode,
+)
 
 __version__ = "0.1.0"

@@ -75,6 +75,13 @@ SIGNATURES = {
     "lbfa_backward_varlen": (_ci, [_vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                    _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci] + [ctypes.POINTER(ctypes.c_int64)] * 8 +
                                   [_cd, _ci, _ci, _ci, _ci, _vp]),
+    "lbfa_kvcache_mean": (_ci, [_vp, _ci, _vp, _vp, _ci, _ci, _ci, _ci, ctypes.POINTER(ctypes.c_int64), _vp]),
+    "lbfa_kvcache_append": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci,
+                                  ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _ci, _vp]),
+    "lbfa_decode_num_splits": (_ci, [_ci, _ci, _ci]),
+    "lbfa_decode_workspace_bytes": (_sz, [_ci] * 7),
+    "lbfa_decode": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci,
+                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _cd, _ci, _ci, _vp]),
 }
 
 _lock = threading.Lock()

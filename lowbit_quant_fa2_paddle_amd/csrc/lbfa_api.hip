@@ -23,6 +23,10 @@ hipError_t launch_cast_bf16_f16(const void* src, void* dst, int B, int H, int S,
 hipError_t launch_absmax(const void* x, int dtype, float* out, int B, int H, int S, int D, const int64_t* st, hipStream_t stream);
 // defined in attn_bwd.hip
 hipError_t launch_attn_bwd(const BwdParams& p, int dtype, bool quant, bool causal, hipStream_t stream);
+// defined in kvcache.hip / attn_decode.hip
+hipError_t launch_kvcache_append(const AppendParams& p, int dtype, int D, hipStream_t stream);
+hipError_t launch_kvcache_mean(const RaggedMeanParams& p, int dtype, int B, int D, hipStream_t stream);
+hipError_t launch_attn_decode(const DecodeParams& p, int dtype, int D, hipStream_t stream);
 }  // namespace lbfa
 
 namespace {
@@ -914,6 +918,143 @@ int lbfa_backward_varlen(const void* q, const void* k, const void* v, const void
   return backward_impl("lbfa_backward_varlen", packed_shape(B, Hq, Hkv, total_q, total_k, max_seqlen_q, max_seqlen_k, D, cu_seqlens_q, cu_seqlens_k),
                        in, grad, dtype, lse, dlse, workspace, workspace_bytes, sm_scale, q_qmax, k_qmax, is_causal, smooth_k,
                        (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// int8 KV cache and split-KV decode attention (kvcache.hip, attn_decode.hip)
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int kDecodeMaxRows = 64;     // query rows per kv head one decode workgroup serves
+constexpr int kDecodeWaves = 1024;     // workgroups (one wave each) that fill the part: 256 CUs x 4 SIMDs
+constexpr int kDecodeMinTiles = 4;     // no key slice shorter than 4 tiles of 64 keys
+constexpr int kDecodeMaxSplits = 256;
+int check_capacity(const char* who, int cap) {
+  return cap > 0 && cap % LBFA_BLKK == 0 ? 0 : fail(LBFA_EINVAL, "%s: capacity must be a positive multiple of 64, got %d", who, cap);
+}
+}  // namespace
+
+int lbfa_kvcache_mean(const void* k_new, int dtype, const int32_t* new_lens, void* km, int B, int Hkv, int T, int D,
+                      const int64_t strides_k[3], void* stream) {
+  const char* who = "lbfa_kvcache_mean";
+  const Operand tk = dense(k_new, strides_k);
+  if (!tk.p || !new_lens || !km) return fail(LBFA_EINVAL, "%s: null pointer", who);
+  if (B <= 0 || Hkv <= 0 || T <= 0) return fail(LBFA_EINVAL, "%s: empty tensor", who);
+  if (int st = check_head_dim(D, false)) return st;
+  if (int st = check_dtype(dtype)) return st;
+  if (int st = check_input16(who, "k_new", tk)) return st;
+  if (B > 65535) return fail(LBFA_EINVAL, "%s: grid too large", who);
+  lbfa::RaggedMeanParams p{};
+  p.k_new = (const unsigned short*)k_new; p.new_lens = new_lens; p.km = (unsigned short*)km;
+  p.kb = tk.st[0]; p.kh = tk.st[1]; p.ks = tk.st[2];
+  p.Hkv = Hkv; p.T = T;
+  g_err[0] = 0;
+  return check_hip(lbfa::launch_kvcache_mean(p, dtype, B, D, (hipStream_t)stream), "lbfa_kvcache_mean launch");
+}
+
+int lbfa_kvcache_append(const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
+                        int8_t* k_codes, float* k_scale, void* v_cache, void* k_tail, const int32_t* seqlens,
+                        int B, int Hkv, int T, int D, int capacity, const int64_t strides_k[3], const int64_t strides_v[3],
+                        int k_qmax, void* stream) {
+  const char* who = "lbfa_kvcache_append";
+  const Operand tk = dense(k_new, strides_k), tv = dense(v_new, strides_v);
+  if (!tk.p || !tv.p || !k_codes || !k_scale || !v_cache || !k_tail || !seqlens) return fail(LBFA_EINVAL, "%s: null pointer", who);
+  if (B <= 0 || Hkv <= 0 || T <= 0) return fail(LBFA_EINVAL, "%s: empty tensor", who);
+  if (int st = check_head_dim(D, false)) return st;
+  if (int st = check_capacity(who, capacity)) return st;
+  if (int st = check_dtype(dtype)) return st;
+  if (int st = check_qmax(who, "k_qmax", k_qmax)) return st;
+  if (int st = check_input16(who, "k_new", tk)) return st;
+  if (int st = check_input16(who, "v_new", tv)) return st;
+  if (!aligned(k_codes, 16) || !aligned(v_cache, 16) || !aligned(k_tail, 16) || !aligned(km, 16) || !aligned(k_scale, 4) ||
+      !aligned(seqlens, 4) || !aligned(new_lens, 4))
+    return fail(LBFA_EINVAL, "%s: cache tensors and km must be 16-byte aligned, k_scale / seqlens / new_lens 4-byte aligned", who);
+  if (B > 65535 || Hkv > 65535) return fail(LBFA_EINVAL, "%s: grid too large", who);
+  lbfa::AppendParams p{};
+  p.k_new = (const unsigned short*)k_new; p.v_new = (const unsigned short*)v_new;
+  p.new_lens = new_lens; p.km = (const unsigned short*)km;
+  p.k_codes = k_codes; p.k_scale = k_scale; p.v = (unsigned short*)v_cache; p.k_tail = (unsigned short*)k_tail;
+  p.seqlens = seqlens;
+  p.kb = tk.st[0]; p.kh = tk.st[1]; p.ks = tk.st[2];
+  p.vb = tv.st[0]; p.vh = tv.st[1]; p.vs = tv.st[2];
+  p.B = B; p.Hkv = Hkv; p.T = T; p.cap = capacity;
+  p.qmax = (float)k_qmax;
+  g_err[0] = 0;
+  return check_hip(lbfa::launch_kvcache_append(p, dtype, D, (hipStream_t)stream), "lbfa_kvcache_append launch");
+}
+
+// The split rule: as many key slices as it takes for B * Hkv * slices one-wave workgroups to reach 1024 (four per CU), but no
+// slice shorter than 4 tiles of 64 keys (below that the per-slice prologue - Q quantiser, first-tile latency - and the
+// partial results outweigh the parallelism), at most 256.  A pure function of its arguments.
+int lbfa_decode_num_splits(int B, int Hkv, int max_seqlen_k) {
+  if (B <= 0 || Hkv <= 0 || max_seqlen_k <= 0) return 1;
+  const int64_t groups = (int64_t)B * Hkv, tiles = ((int64_t)max_seqlen_k + LBFA_BLKK - 1) / LBFA_BLKK;
+  int64_t s = (kDecodeWaves + groups - 1) / groups;
+  if (s > tiles / kDecodeMinTiles) s = tiles / kDecodeMinTiles;
+  if (s > kDecodeMaxSplits) s = kDecodeMaxSplits;
+  return s < 1 ? 1 : (int)s;
+}
+
+size_t lbfa_decode_workspace_bytes(int B, int Hq, int Hkv, int Sq, int D, int max_seqlen_k, int num_splits) {
+  if (B <= 0 || Hq <= 0 || Hkv <= 0 || Sq <= 0 || (D != 64 && D != 128) || Hq % Hkv != 0 || num_splits < 0) return 0;
+  const int splits = num_splits ? num_splits : lbfa_decode_num_splits(B, Hkv, max_seqlen_k);
+  if (splits <= 1) return 0;  // one slice writes O itself
+  const size_t rows = (size_t)B * Hkv * splits * ((size_t)Sq * (Hq / Hkv));
+  Bump ws;
+  ws.take(rows * D * sizeof(float));  // un-normalised partial O
+  ws.take(rows * 4 * sizeof(float));  // m, l, q . km
+  return ws.used;
+}
+
+int lbfa_decode(const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const void* v_cache, const void* km,
+                const int32_t* seqlens, void* o, float* lse, void* workspace, size_t workspace_bytes,
+                int B, int Hq, int Hkv, int Sq, int D, int capacity, int max_seqlen_k, int num_splits,
+                const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream) {
+  const char* who = "lbfa_decode";
+  const Operand tq = dense(q, strides_q), to = dense(o, strides_o);
+  if (!tq.p || !to.p || !k_codes || !k_scale || !v_cache || !seqlens) return fail(LBFA_EINVAL, "%s: null pointer", who);
+  if (B <= 0 || Hq <= 0 || Hkv <= 0 || Sq <= 0) return fail(LBFA_EINVAL, "%s: empty tensor", who);
+  if (int st = check_head_dim(D, false)) return st;
+  if (int st = check_gqa(Hq, Hkv)) return st;
+  const int64_t M = (int64_t)Sq * (Hq / Hkv);
+  if (M > kDecodeMaxRows)
+    return fail(LBFA_EINVAL, "%s: Sq * (Hq / Hkv) = %lld query rows per kv head, the limit is %d (longer queries belong on the dense operator)",
+                who, (long long)M, kDecodeMaxRows);
+  if (int st = check_capacity(who, capacity)) return st;
+  if (max_seqlen_k < 1 || max_seqlen_k > capacity)
+    return fail(LBFA_EINVAL, "%s: max_seqlen_k must be in [1, capacity], got %d (capacity %d)", who, max_seqlen_k, capacity);
+  if (num_splits < 0 || num_splits > 65535) return fail(LBFA_EINVAL, "%s: num_splits must be in [0, 65535] (0: chosen by lbfa_decode_num_splits), got %d", who, num_splits);
+  if (int st = check_dtype(dtype)) return st;
+  if (int st = check_qmax(who, "q_qmax", q_qmax)) return st;
+  if (!(sm_scale > 0.0)) return fail(LBFA_EINVAL, "%s: sm_scale must be positive", who);
+  if (int st = check_input16(who, "q", tq)) return st;
+  if (!aligned(to, 8, 4)) return fail(LBFA_EINVAL, "%s: o must be 8-byte aligned with strides that are multiples of 4 elements", who);
+  if (!aligned(k_codes, 16) || !aligned(v_cache, 16) || !aligned(km, 16) || !aligned(k_scale, 4) || !aligned(seqlens, 4) || !aligned(lse, 4))
+    return fail(LBFA_EINVAL, "%s: cache tensors and km must be 16-byte aligned, k_scale / seqlens / lse 4-byte aligned", who);
+  const int splits = num_splits ? num_splits : lbfa_decode_num_splits(B, Hkv, max_seqlen_k);
+  const size_t need = lbfa_decode_workspace_bytes(B, Hq, Hkv, Sq, D, max_seqlen_k, splits);
+  if (need) {
+    if (int st = check_workspace(who, workspace, workspace_bytes, need)) return st;
+    if (!workspace) return fail(LBFA_EINVAL, "%s: null pointer", who);
+  }
+  if (B > 65535 || Hkv > 65535) return fail(LBFA_EINVAL, "%s: grid too large", who);
+  lbfa::DecodeParams p{};
+  p.q = (const unsigned short*)q; p.k_codes = k_codes; p.k_scale = k_scale; p.v = (const unsigned short*)v_cache;
+  p.km = lse ? (const unsigned short*)km : nullptr;  // km only enters the LSE correction
+  p.seqlens = seqlens; p.o = o; p.lse = lse;
+  p.qb = tq.st[0]; p.qh = tq.st[1]; p.qs = tq.st[2];
+  p.ob = to.st[0]; p.oh = to.st[1]; p.os = to.st[2];
+  p.B = B; p.Hq = Hq; p.Hkv = Hkv; p.Sq = Sq; p.group = Hq / Hkv; p.M = (int)M;
+  p.cap = capacity; p.max_k = max_seqlen_k; p.splits = splits; p.causal = is_causal ? 1 : 0;
+  p.q_sm_scale = (float)(sm_scale * 1.44269504);  // ONE rounding of the double product, as lbfa_forward
+  p.q_qmax = (float)q_qmax;
+  p.corr_scale = (float)sm_scale;
+  if (splits > 1) {
+    const size_t rows = (size_t)B * Hkv * splits * (size_t)M;
+    p.ws_acc = (float*)workspace;
+    p.ws_ml = (float*)((char*)workspace + align256(rows * D * sizeof(float)));
+  }
+  g_err[0] = 0;
+  return check_hip(lbfa::launch_attn_decode(p, dtype, D, (hipStream_t)stream), "lbfa_decode launch");
 }
 
 }  // extern "C"

@@ -174,4 +174,46 @@ struct BwdParams {
   int total_q, total_k;
 };
 
+// int8 KV cache (kvcache.hip): cache tensors are contiguous, [B, Hkv, cap, D] codes / fp16 V, [B, Hkv, cap / 64] scales,
+// [B, Hkv, 64, D] raw rows of the open block, [B, Hkv, D] km; the new rows come through strides {batch, head, seq}
+struct AppendParams {
+  const unsigned short* k_new;
+  const unsigned short* v_new;
+  const int* new_lens;          // [B] or null (every sequence appends T rows)
+  const unsigned short* km;     // storage dtype or null
+  int8_t* k_codes;
+  float* k_scale;
+  unsigned short* v;
+  unsigned short* k_tail;
+  const int* seqlens;           // [B], read on the device, not advanced
+  int64_t kb, kh, ks, vb, vh, vs;
+  int B, Hkv, T, cap;
+  float qmax;
+};
+struct RaggedMeanParams {
+  const unsigned short* k_new;
+  const int* new_lens;
+  unsigned short* km;
+  int64_t kb, kh, ks;
+  int Hkv, T;
+};
+
+// decode attention over the cache (attn_decode.hip): M = Sq * group query rows per (batch, kv head), row r = query head
+// hk * group + r / Sq, position r % Sq
+struct DecodeParams {
+  const unsigned short* q;
+  const int8_t* k_codes;
+  const float* k_scale;
+  const unsigned short* v;
+  const unsigned short* km;  // null: no LSE correction
+  const int* seqlens;
+  void* o;
+  float* lse;                // [B, Hq, Sq] natural log, or null
+  float* ws_acc;             // [B, Hkv, splits, M, D] un-normalised partial O (splits > 1)
+  float* ws_ml;              // [B, Hkv, splits, M, 4]: m, l, dtype(q . km), unused
+  int64_t qb, qh, qs, ob, oh, os;
+  int B, Hq, Hkv, Sq, group, M, cap, max_k, splits, causal;
+  float q_sm_scale, q_qmax, corr_scale;
+};
+
 }  // namespace lbfa

@@ -1,0 +1,190 @@
+"""Int8 KV cache and split-KV decode attention for short queries (torch, forward only).
+
+`LowbitKVCache` keeps K as the int8 codes and per-64-key scales the dense operators' K quantiser produces (bit for bit: a
+prefill appended to an empty cache holds exactly the codes `lowbit_fa_qk_int8_pv_fp16_triton` would compute), V as fp16, and
+is appended to in place (`lbfa_kvcache_append`).  `lowbit_fa_decode` attends a few new queries (Sq * Hq / Hkv <= 64 rows per kv
+head) to the cache with one split-KV kernel (`lbfa_decode`): K and V are read once per GQA group, nothing is re-quantised.
+
+Not here: paged / block-table caches, an fp8 V cache (its per-channel scale needs the whole sequence), nibble-packed int4
+(the +-7 codes take a byte each), a backward through the cache, Paddle tensors.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+from . import _lib
+from . import quant_per_block as _qpb
+from ._tensor import ops_for
+
+
+def _padded_head_dim(d: int) -> int:
+    if d > 128:
+        raise ValueError(f"Unsupported head_dim: {d}")
+    return 64 if d <= 64 else 128
+
+
+class LowbitKVCache:
+    """Pre-allocated cache of `batch` sequences of up to `capacity` keys (rounded up to a multiple of 64).
+
+    State (all on `device`): k_codes int8 [B, Hkv, cap, Dp], k_scale fp32 [B, Hkv, cap / 64], v fp16 [B, Hkv, cap, Dp],
+    k_tail [B, Hkv, 64, Dp] (raw rows of the open 64-key block), km [B, Hkv, Dp] or None, seqlens int32 [B]; Dp = head_dim
+    zero-padded to 64 / 128.  `km`, the smooth-K mean, is taken from the FIRST append and fixed from then on.
+    No host read of `seqlens` happens anywhere: the host only tracks an upper bound of the lengths (the rows offered so far)."""
+
+    def __init__(self, batch: int, num_kv_heads: int, head_dim: int, capacity: int, dtype, device, k_bits: int = 8,
+                 smooth_k: bool = True):
+        import torch
+        if k_bits not in (8, 4):
+            raise ValueError(f"k_bits must be 8 or 4, got {k_bits}")
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError("dtype must be torch.float16 or torch.bfloat16")
+        if batch <= 0 or num_kv_heads <= 0 or capacity <= 0:
+            raise ValueError("batch, num_kv_heads and capacity must be positive")
+        self.batch, self.num_kv_heads, self.head_dim = int(batch), int(num_kv_heads), int(head_dim)
+        self.padded_head_dim = _padded_head_dim(self.head_dim)
+        self.capacity = (int(capacity) + _lib.BLKK - 1) // _lib.BLKK * _lib.BLKK
+        self.dtype, self.device = dtype, torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("LowbitKVCache lives on an AMD GPU (gfx950) only; there is no CPU fallback.")
+        self.k_qmax = 127 if k_bits == 8 else 7
+        self.smooth_k = bool(smooth_k)
+        B, H, C, D = self.batch, self.num_kv_heads, self.capacity, self.padded_head_dim
+        self.k_codes = torch.zeros((B, H, C, D), dtype=torch.int8, device=self.device)
+        self.k_scale = torch.zeros((B, H, C // _lib.BLKK), dtype=torch.float32, device=self.device)
+        self.v = torch.zeros((B, H, C, D), dtype=torch.float16, device=self.device)
+        self.k_tail = torch.zeros((B, H, _lib.BLKK, D), dtype=dtype, device=self.device)
+        self.km = torch.zeros((B, H, D), dtype=dtype, device=self.device) if self.smooth_k else None
+        self.seqlens = torch.zeros((B,), dtype=torch.int32, device=self.device)
+        self.max_seqlen = 0  # host upper bound of seqlens
+        self._has_km = False
+
+    def append(self, k, v, tensor_layout: str = "HND", new_lens=None):
+        """Append k, v [B, Hkv, T, D] ("HND") or [B, T, Hkv, D] ("NHD"); sequence b takes the first new_lens[b] rows (an int32
+        device tensor [B], None: all T).  Returns self."""
+        ops = ops_for(k)
+        torch = ops.torch
+        if tensor_layout not in ("HND", "NHD"):
+            raise ValueError(f"Unknown tensor layout: {tensor_layout}")
+        if k.dtype != self.dtype or v.dtype != self.dtype:
+            raise ValueError("k and v must have the dtype of the cache")
+        if k.device != self.device or v.device != self.device:
+            raise ValueError("k and v must be on the device of the cache")
+        if tuple(k.shape) != tuple(v.shape) or k.dim() != 4:
+            raise ValueError("k and v must be 4-D tensors of the same shape")
+        pad = self.padded_head_dim - self.head_dim
+        if k.shape[-1] != self.head_dim:
+            raise ValueError(f"head_dim {k.shape[-1]} does not match the cache ({self.head_dim})")
+        if pad:  # only the new tokens are padded
+            k, v = ops.pad_last(k, pad), ops.pad_last(v, pad)
+        if k.stride(-1) != 1:
+            k = k.contiguous()
+        if v.stride(-1) != 1:
+            v = v.contiguous()
+        (B, H, T), k3 = _qpb._bhs(ops.shape(k), ops.strides(k), tensor_layout)
+        (_, _, _), v3 = _qpb._bhs(ops.shape(v), ops.strides(v), tensor_layout)
+        if B != self.batch or H != self.num_kv_heads:
+            raise ValueError(f"expected batch {self.batch} and {self.num_kv_heads} kv heads, got {B} and {H}")
+        if T == 0:
+            return self
+        if self.max_seqlen + T > self.capacity:
+            raise ValueError(f"appending {T} tokens to at most {self.max_seqlen} would pass the capacity {self.capacity}")
+        if new_lens is not None:
+            new_lens = new_lens.to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(new_lens.shape) != (self.batch,):
+                raise ValueError("new_lens must have one entry per sequence")
+        lib = _lib.load()
+        D, code = self.padded_head_dim, ops.dtype_code(k)
+        with ops.device_guard(k):
+            stream = ops.stream(k)
+            if self.smooth_k and not self._has_km:
+                if new_lens is None:  # the mean of the dense operators: the codes of a prefill are theirs
+                    ws_bytes = lib.lbfa_mean_seq_workspace_bytes(B, H, T, D)
+                    ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=self.device)
+                    _lib.check(lib.lbfa_mean_seq(k.data_ptr(), code, self.km.data_ptr(), ws.data_ptr(), ws_bytes, B, H, T, D,
+                                                 _lib.strides3(k3), stream), lib)
+                else:
+                    _lib.check(lib.lbfa_kvcache_mean(k.data_ptr(), code, new_lens.data_ptr(), self.km.data_ptr(), B, H, T, D,
+                                                     _lib.strides3(k3), stream), lib)
+                self._has_km = True
+            _lib.check(lib.lbfa_kvcache_append(k.data_ptr(), v.data_ptr(), code, new_lens.data_ptr() if new_lens is not None else None,
+                                               self.km.data_ptr() if self.smooth_k else None, self.k_codes.data_ptr(),
+                                               self.k_scale.data_ptr(), self.v.data_ptr(), self.k_tail.data_ptr(),
+                                               self.seqlens.data_ptr(), B, H, T, D, self.capacity, _lib.strides3(k3),
+                                               _lib.strides3(v3), self.k_qmax, stream), lib)
+            # the kernel reads seqlens and does not advance it
+            if new_lens is None:
+                self.seqlens += T
+            else:
+                self.seqlens += torch.clamp(new_lens, 0, T)
+        self.max_seqlen += T
+        return self
+
+    def dequantized_k(self):
+        """Debugging aid (torch ops, read-only): fp32 [B, Hkv, capacity, head_dim] = codes * scale (+ km).  Rows at or past
+        seqlens[b] are meaningless."""
+        k = self.k_codes.float() * self.k_scale.repeat_interleave(_lib.BLKK, dim=2)[..., None]
+        if self.km is not None:
+            k = k + self.km.float()[:, :, None, :]
+        return k[..., :self.head_dim]
+
+
+def lowbit_fa_decode(q, cache: LowbitKVCache, tensor_layout: str = "HND", is_causal: bool = False,
+                     sm_scale: Optional[float] = None, return_lse: bool = False, num_splits: int = 0, q_bits: int = 8):
+    """Attention of the new queries q [B, Hq, Sq, D] ("HND") or [B, Sq, Hq, D] ("NHD") to everything in `cache` (the keys of
+    these queries appended first).  Sq * (Hq / Hkv) <= 64.  `is_causal`: bottom-right aligned, query i sees keys
+    < seqlens[b] - Sq + 1 + i.  `num_splits`: key slices (0: chosen by `lbfa_decode_num_splits`); results are bitwise
+    reproducible for a given value.  Returns o (shape and dtype of q) and, with `return_lse`, the natural-log LSE [B, Hq, Sq]
+    fp32.  A sequence with no keys gets zeros and -inf.  Forward only."""
+    ops = ops_for(q)
+    if ops.name != "torch":
+        raise TypeError("lowbit_fa_decode takes torch tensors")
+    torch = ops.torch
+    if not isinstance(cache, LowbitKVCache):
+        raise TypeError("cache must be a LowbitKVCache")
+    if torch.is_grad_enabled() and q.requires_grad:
+        raise RuntimeError("lowbit_fa_decode is forward-only: there is no backward through the KV cache "
+                           "(call it under torch.no_grad() or detach q)")
+    if tensor_layout not in ("HND", "NHD"):
+        raise ValueError(f"Unknown tensor layout: {tensor_layout}")
+    if q_bits not in (8, 4):
+        raise ValueError(f"q_bits must be 8 or 4, got {q_bits}")
+    if q.dtype != cache.dtype:
+        raise ValueError("q must have the dtype of the cache")
+    if q.device != cache.device:
+        raise ValueError("q must be on the device of the cache")
+    if q.dim() != 4 or q.shape[-1] != cache.head_dim:
+        raise ValueError(f"q must be 4-D with head_dim {cache.head_dim}")
+    head_dim_og = cache.head_dim
+    if sm_scale is None:
+        sm_scale = 1.0 / head_dim_og ** 0.5
+    pad = cache.padded_head_dim - head_dim_og
+    if pad:
+        q = ops.pad_last(q, pad)
+    if q.stride(-1) != 1:
+        q = q.contiguous()
+    qshape = ops.shape(q)
+    (B, Hq, Sq), q3 = _qpb._bhs(qshape, ops.strides(q), tensor_layout)
+    if B != cache.batch:
+        raise ValueError(f"expected batch {cache.batch}, got {B}")
+    o = ops.empty(qshape, q.dtype, q)
+    (_, _, _), o3 = _qpb._bhs(qshape, ops.strides(o), tensor_layout)
+    lse = ops.empty((B, Hq, Sq), ops.float32, q) if return_lse else None
+    if 0 in qshape:
+        return (o[..., :head_dim_og], lse) if return_lse else o[..., :head_dim_og]
+    lib = _lib.load()
+    Hkv, D = cache.num_kv_heads, cache.padded_head_dim
+    max_k = max(1, min(cache.max_seqlen, cache.capacity))
+    ws_bytes = lib.lbfa_decode_workspace_bytes(B, Hq, Hkv, Sq, D, max_k, int(num_splits))
+    ws = ops.empty((max(ws_bytes, 16),), ops.uint8, q)
+    with ops.device_guard(q):
+        _lib.check(lib.lbfa_decode(q.data_ptr(), ops.dtype_code(q), cache.k_codes.data_ptr(), cache.k_scale.data_ptr(),
+                                   cache.v.data_ptr(), cache.km.data_ptr() if cache.km is not None else None,
+                                   cache.seqlens.data_ptr(), o.data_ptr(), lse.data_ptr() if return_lse else None,
+                                   ws.data_ptr(), ws_bytes, B, Hq, Hkv, Sq, D, cache.capacity, max_k, int(num_splits),
+                                   _lib.strides3(q3), _lib.strides3(o3), float(sm_scale), 127 if q_bits == 8 else 7,
+                                   1 if is_causal else 0, ops.stream(q)), lib)
+    o = o[..., :head_dim_og]
+    return (o, lse) if return_lse else o
+
+
+sageattn_decode = lowbit_fa_decode

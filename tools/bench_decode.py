@@ -1,0 +1,141 @@
+#!/usr/bin/env python3
+"""Event-timed decode step (Sq = 1) over the int8 KV cache against the other ways to compute it on the same GPU.
+
+    python tools/bench_decode.py [--steps K] [--warmup W] [--shapes B1_S4K,...] [--out FILE]
+
+Shapes: Hq 32 / Hkv 8, D 128, Sq 1, B in {1, 8, 64} x context in {4K, 32K, 128K}.  Arms, alternated step by step in one process
+(so drift hits all alike), each step bracketed by HIP events; median and the 10th .. 90th percentile spread per arm:
+  decode       `lowbit_fa_decode` on a filled `LowbitKVCache`, num_splits chosen by lbfa_decode_num_splits
+  decode_1     the same with num_splits = 1
+  dense_int8   the dense int8 operator at Sq = 1 on the 16-bit K / V (`lowbit_fa_qk_int8_pv_fp16_triton`): what the library offered
+               for a decode step before the cache existed - it re-smooths and re-quantises K on every call
+  sdpa_fp16    torch's scaled_dot_product_attention on the fp16 K / V, the Hq / Hkv query heads of a kv head as its query rows
+Traffic model of `decode`: per key and kv head D code bytes + 2 D bytes of V, one fp32 scale per 64 keys, plus q and o - over
+the time of the whole CALL (host launch path and combine included; the streaming kernel alone: the profiler run below), as a
+share of the 6.3 TB/s streaming ceiling of the part.
+Prints one JSON document (and writes it to --out).
+
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/bench_decode.py --calls-only [--shapes ...]
+
+`--calls-only` fills the cache and makes ten calls of `decode` and of `decode_1` per shape, untimed: the run to put under the
+profiler for per-kernel times (profiles/decode_kernel_trace.json), separate from the timed run.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+HQ, HKV, D = 32, 8, 128
+HBM_CEILING = 6.3e12
+SHAPES = [(f"B{b}_S{s // 1024}K", b, s) for b in (1, 8, 64) for s in (4096, 32768, 131072)]
+
+
+def _pct(xs, p):
+    xs = sorted(xs)
+    return xs[min(len(xs) - 1, int(round(p * (len(xs) - 1))))]
+
+
+def run_shape(name, B, S, steps, warmup):
+    import lowbit_quant_fa2_paddle_amd as lb
+    from lowbit_quant_fa2_paddle_amd import _lib
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    k = torch.randn((B, HKV, S, D), device=dev, dtype=torch.float16)
+    v = torch.randn((B, HKV, S, D), device=dev, dtype=torch.float16)
+    q = torch.randn((B, HQ, 1, D), device=dev, dtype=torch.float16)
+    cache = lb.LowbitKVCache(B, HKV, D, S, torch.float16, dev).append(k, v)
+    q_rows = q.view(B, HKV, HQ // HKV, D)  # the query heads of a kv head as query rows of one head
+    arms = {
+        "decode": lambda: lb.lowbit_fa_decode(q, cache),
+        "decode_1": lambda: lb.lowbit_fa_decode(q, cache, num_splits=1),
+        "dense_int8": lambda: lb.lowbit_fa_qk_int8_pv_fp16_triton(q, k, v),
+        "sdpa_fp16": lambda: F.scaled_dot_product_attention(q_rows, k, v),
+    }
+    with torch.no_grad():
+        ref = arms["sdpa_fp16"]().view(B, HQ, 1, D).float()
+        err = {a: float((arms[a]().float() - ref).abs().max()) for a in ("decode", "decode_1", "dense_int8")}
+        for _ in range(warmup):
+            for fn in arms.values():
+                fn()
+        ts = {a: [] for a in arms}
+        for _ in range(steps):
+            for a, fn in arms.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                ts[a].append(e0.elapsed_time(e1) * 1e3)
+    splits = _lib.load().lbfa_decode_num_splits(B, HKV, S)
+    bytes_needed = B * HKV * (S * 3 * D + (S // 64) * 4) + 2 * B * HQ * D * 2
+    rec = dict(shape=name, B=B, Hq=HQ, Hkv=HKV, Sq=1, context=S, D=D, num_splits=splits, bytes_needed=bytes_needed,
+               max_abs_diff_vs_sdpa=err)
+    for a in arms:
+        rec[a + "_us"] = statistics.median(ts[a])
+        rec[a + "_us_p10_p90"] = [_pct(ts[a], 0.1), _pct(ts[a], 0.9)]
+    rec["decode_share_of_hbm_ceiling"] = bytes_needed / (rec["decode_us"] * 1e-6) / HBM_CEILING
+    for a in ("decode_1", "dense_int8", "sdpa_fp16"):
+        rec[f"speedup_vs_{a}"] = rec[a + "_us"] / rec["decode_us"]
+    # faster than the dense operator by more than the run-to-run spread: its fastest decile against our slowest
+    rec["beats_dense_int8_beyond_spread"] = rec["dense_int8_us_p10_p90"][0] > rec["decode_us_p10_p90"][1]
+    return rec
+
+
+def calls_only(B, S, calls=10):
+    import lowbit_quant_fa2_paddle_amd as lb
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    k = torch.randn((B, HKV, S, D), device=dev, dtype=torch.float16)
+    v = torch.randn((B, HKV, S, D), device=dev, dtype=torch.float16)
+    q = torch.randn((B, HQ, 1, D), device=dev, dtype=torch.float16)
+    cache = lb.LowbitKVCache(B, HKV, D, S, torch.float16, dev).append(k, v)
+    for _ in range(calls):
+        lb.lowbit_fa_decode(q, cache)
+        lb.lowbit_fa_decode(q, cache, num_splits=1)
+    torch.cuda.synchronize()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--shapes", default=",".join(s[0] for s in SHAPES))
+    ap.add_argument("--calls-only", action="store_true", help="untimed calls for a profiler run")
+    a = ap.parse_args()
+    want = a.shapes.split(",")
+    if a.calls_only:
+        for name, B, S in SHAPES:
+            if name in want:
+                calls_only(B, S)
+                torch.cuda.empty_cache()
+        return
+    res = dict(label="builder measurement", tool="tools/bench_decode.py", device=torch.cuda.get_device_name(0),
+               torch=torch.__version__, steps=a.steps, warmup=a.warmup,
+               timing="HIP events around one call per arm, arms alternated within every step, median and 10th..90th percentile; "
+                      "the times include the host's launch path (one to three launches per call)",
+               results=[])
+    for name, B, S in SHAPES:
+        if name in want:
+            try:
+                res["results"].append(run_shape(name, B, S, a.steps, a.warmup))
+            except torch.cuda.OutOfMemoryError as e:  # "where memory allows"
+                res["results"].append(dict(shape=name, skipped=f"out of memory: {str(e)[:80]}"))
+            torch.cuda.empty_cache()
+            print(json.dumps(res["results"][-1]), flush=True)
+    txt = json.dumps(res, indent=1)
+    print(txt)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(txt + "\n")
+
+
+if __name__ == "__main__":
+    main()
