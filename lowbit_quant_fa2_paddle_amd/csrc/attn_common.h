@@ -112,15 +112,126 @@ constexpr float kMagic = 12582912.0f;  // 1.5 * 2^23: int32 accumulator bits == 
 constexpr int kMagicBits = 0x4B400000;
 constexpr int kQInt8 = 3;  // QT of the attention kernel: int8 codes; LBFA_F16 / LBFA_BF16 = un-quantised Q and K
 
-// bf16 pairs -> fp16 pairs, in place (a 16-byte chunk = 8 elements)
-__device__ __forceinline__ u32x4 bf16x8_to_f16x8(u32x4 val) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float lo = __uint_as_float(val[e] << 16), hi = __uint_as_float(val[e] & 0xffff0000u);
-    const f16x2 pk = f16x2{(_Float16)lo, (_Float16)hi};
-    val[e] = __builtin_bit_cast(unsigned, pk);
+// ---- prologue and epilogue shared by the two forward kernels (attn_fwd.hip: fp8 PV, attn_fwd16.hip: fp16 P) -----------------
+// Which (q-block, batch, head, kv head) this workgroup takes: XCD remap of the 1-D grid, causal: heaviest q-blocks of a head first.
+struct WorkItem {
+  int qt, b, h, hk;
+};
+template <bool CAUSAL>
+__device__ __forceinline__ WorkItem work_item(const AttnParams& p) {
+  const unsigned w_id = xcd_remap(blockIdx.x, gridDim.x);
+  int qt = (int)(w_id % (unsigned)p.nQ);
+  const int bh = (int)(w_id / (unsigned)p.nQ);
+  if constexpr (CAUSAL) qt = p.nQ - 1 - qt;
+  const int b = bh / p.Hq, h = bh % p.Hq;
+  return WorkItem{qt, b, h, h / p.group};
+}
+
+// The problem a workgroup works on: batch entry b of a dense call, or sequence b of a packed variable-length batch
+// (attn_qk_int8_block_varlen.py:125-141).  Offsets in elements, without the head term.
+struct Problem {
+  int Sq, Sk, nK;
+  int64_t q_off, k_off, v_off, o_off;
+  int64_t qsc_base, ksc_base;  // scale index of block 0 of head 0
+  int64_t lse_base;            // LSE index of query row 0: [B,Hq,Sq], packed [Hq, total_q]
+  int vec_b;                   // which q_dot_vec set: one per batch entry, packed: one mean over all tokens
+  bool no_work;                // this q-block lies past the end of the sequence: return, whole workgroup, before any barrier
+};
+__device__ __forceinline__ Problem locate_problem(const AttnParams& p, int b, int h, int qt) {
+  Problem r;
+  r.Sq = p.Sq; r.Sk = p.Sk; r.nK = p.nK;
+  r.q_off = (int64_t)b * p.qb; r.k_off = (int64_t)b * p.kb; r.v_off = (int64_t)b * p.vb; r.o_off = (int64_t)b * p.ob;
+  r.qsc_base = (int64_t)b * p.qsc_b; r.ksc_base = (int64_t)b * p.ksc_b;
+  r.lse_base = ((int64_t)b * p.Hq + h) * p.Sq;
+  r.vec_b = b;
+  r.no_work = false;
+  if (p.cu_q != nullptr) {
+    const int q0 = p.cu_q[b], k0 = p.cu_k[b];
+    r.lse_base = (int64_t)h * p.lse_hs + q0;
+    r.vec_b = 0;
+    // max_seqlen_q / max_seqlen_k (p.Sq / p.Sk) size the grid and the padded scale rows: a sequence longer than the
+    // caller's maximum is cut there, so that every access stays inside the buffers sized from those maxima
+    r.Sq = min(p.cu_q[b + 1] - q0, p.Sq);
+    r.Sk = min(p.cu_k[b + 1] - k0, p.Sk);
+    r.no_work = qt * 128 >= r.Sq;
+    r.nK = (r.Sk + 63) >> 6;
+    r.q_off = (int64_t)q0 * p.qs;
+    r.k_off = (int64_t)k0 * p.ks;
+    r.v_off = (int64_t)k0 * p.vs;
+    r.o_off = (int64_t)q0 * p.os;
+    if (p.cu_qscale != nullptr) {
+      r.qsc_base = (int64_t)p.cu_qscale[b] * p.qsc_b;
+      r.ksc_base = (int64_t)p.cu_kscale[b] * p.ksc_b;
+    }
   }
-  return val;
+  return r;
+}
+
+// LDS-DMA fetch of tile j of one operand: NCH passes of 256 threads x 16 bytes, written linearly from lds_dst (wave-uniform, + 16
+// bytes per lane, implicit).  The descriptor is re-based per tile with scalar arithmetic and covers what is left of the operand's
+// `bytes` (< 2 GiB, checked by the C ABI), so rows past the end read as zeros with no per-lane guard; the look-ahead past either
+// end (!in_range) gets a window of 0 bytes.  goff: the thread's loop-invariant source offset (swizzle included), gstep: bytes
+// between a thread's chunks.
+typedef __attribute__((address_space(3))) void* lds_void_ptr;
+template <int NCH>
+__device__ __forceinline__ void fetch_tile(const char* base, int bytes, int tile_stride, int j, bool in_range, char* lds_dst,
+                                           unsigned goff, unsigned gstep) {
+  const int off = in_range ? j * tile_stride : 0;
+  const int rem = in_range ? max(0, bytes - off) : 0;
+  const __amdgpu_buffer_rsrc_t rs = make_rsrc(base + off, (unsigned)rem);
+#pragma unroll
+  for (int i = 0; i < NCH; ++i)
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_ptr)(lds_dst + i * 4096), 16, (int)goff, (int)(i * gstep), 0, 0);
+}
+
+// Processing order of the key tiles.  Non-causal: every other ROUND of Q blocks of a head (kRound = the workgroups one XCD runs
+// at a time) walks the key tiles from the last one down (see attn_fwd.hip); the direction depends on the Q block index only.
+template <bool CAUSAL, int kRound>
+__device__ __forceinline__ bool walks_back(int Sk, int qt) {
+  return !CAUSAL && ((Sk & 63) == 0) && (((qt / kRound) & 1) != 0);  // workgroup-uniform
+}
+__device__ __forceinline__ int tile_at(bool rev, int nK, int i) { return rev ? nK - 1 - i : i; }  // i-th tile processed
+
+// Scale grid of the exact bias folding (see attn_fwd.hip): the largest k_scale of this (batch, kv head) - lane l has tile l's in
+// ks_first - and log2 of the power of two G chosen from the largest dequantisation scale.
+__device__ __forceinline__ float max_k_scale(const float* ksc, int ksc_blk, int nK, int lane, float ks_first) {
+  float ks_max = ks_first;
+  for (int i = lane + 64; i < nK; i += 64) ks_max = fmaxf(ks_max, ksc[i * ksc_blk]);
+  return fmaxf(wave_max_nonneg(ks_max), 1e-30f);  // scales are positive (the quantiser floors amax)
+}
+__device__ __forceinline__ int grid_exponent(float sc_max) {
+  return __builtin_amdgcn_readfirstlane((int)((__float_as_uint(1.25f * kMagic * sc_max) >> 23) & 0xff) - 127 + 1 - 21);
+}
+// lane l: the raw k_scale of tile j0 + l (0 past the end)
+__device__ __forceinline__ float k_scale_of_lane(const float* ksc, int ksc_blk, int nK, int j0, int lane, float ks_first) {
+  const int jt = j0 + lane;
+  return j0 == 0 ? ks_first : (jt < nK ? ksc[jt * ksc_blk] : 0.f);
+}
+// ... and the dequantisation scale the tile loop uses for it: un-rounded for a `wide` wave, else on the grid of step g = 1 / invg.
+// At least 1e-30 / one grid step: a block whose scale is < 2^-22 of the largest one (an all-zero K block) must not get sc = 0, or
+// a masked key (tv = -inf) would turn into fma(-inf, 0, c1) = NaN
+__device__ __forceinline__ float wide_scale(float qsc, float ks_l) { return fmaxf(qsc * ks_l, 1e-30f); }
+__device__ __forceinline__ float tile_scale(float qsc, float ks_l, float g, float invg, bool wide) {
+  float sc = fmaxf(__builtin_rintf(qsc * ks_l * invg), 1.0f) * g;
+  if (wide) sc = wide_scale(qsc, ks_l);  // (a statement, not a select: the select cost the D = 128 causal instances registers)
+  return sc;
+}
+
+// LSE of one query row from its base-2 value: lse_out = lse2 * lse_scale + corr * lse_corr_scale (src/core.py:344-350), corr = the
+// q . km computed in the kernel (QQ) or read from lse_corr
+template <bool QQ>
+__device__ __forceinline__ void store_lse(const AttnParams& p, int64_t li, float lse2, float row_corr) {
+  float ls = lse2 * p.lse_scale;
+  if constexpr (QQ) ls += row_corr * p.lse_corr_scale;  // 0 when there is no smoothing vector
+  else if (p.lse_corr != nullptr) ls += p.lse_corr[li] * p.lse_corr_scale;
+  p.lse[li] = ls;
+}
+
+// host: launches the causal or the plain instance of a forward kernel, one workgroup of 256 threads per 128-row Q block
+template <typename Kernel>
+inline hipError_t launch_fwd(Kernel causal_kernel, Kernel plain_kernel, int causal, const AttnParams& p, hipStream_t stream) {
+  hipLaunchKernelGGL(causal ? causal_kernel : plain_kernel, dim3((unsigned)p.B * p.Hq * p.nQ), dim3(256), 0, stream, p);
+  return hipGetLastError();
 }
 
 }  // namespace lbfa

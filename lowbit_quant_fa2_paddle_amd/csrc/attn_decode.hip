@@ -78,6 +78,8 @@ __global__ __launch_bounds__(64) void attn_decode_kernel(DecodeParams p) {
         }
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
+          // (spelled out, not elem16 / quant_codes16 as in the forward kernels: behind either helper the compiler swaps the operands
+          // of an add in this kernel's LSE epilogue, and the kernel has to stay the parent's instruction for instruction)
           const unsigned w[4] = {raw[hf].x, raw[hf].y, raw[hf].z, raw[hf].w};
           const unsigned mw[4] = {kmr[hf].x, kmr[hf].y, kmr[hf].z, kmr[hf].w};
 #pragma unroll
@@ -105,7 +107,7 @@ __global__ __launch_bounds__(64) void attn_decode_kernel(DecodeParams p) {
       const int r0 = row[rb] - sq[rb];  // first row of this row's query head
       if (valid[rb])
         for (int j = 0; j < p.Sq; ++j) am = fmaxf(am, srow[r0 + j]);
-      const float scale = fmaxf(am, 1e-7f) / p.q_qmax;
+      const float scale = block_scale(am, p.q_qmax);
       qsc[rb] = scale;
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
@@ -114,13 +116,8 @@ __global__ __launch_bounds__(64) void attn_decode_kernel(DecodeParams p) {
         for (int g4 = 0; g4 < 4; ++g4) {
           int qv[4];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float y = xq[rb][s][4 * g4 + e] / scale;  // correctly rounded quotient, as the quantiser's
-            qv[e] = (int)(y + __builtin_copysignf(0.5f, y));
-          }
-          const unsigned p01 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pk_i16(qv[0], qv[1]));
-          const unsigned p23 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pk_i16(qv[2], qv[3]));
-          wd[g4] = __builtin_amdgcn_perm(p23, p01, 0x06040200u);
+          for (int e = 0; e < 4; ++e) qv[e] = quant_code<false>(xq[rb][s][4 * g4 + e], scale, 0.f);  // the plain division
+          wd[g4] = pack4_i8(qv);
         }
         qf[rb][s] = i32x4{(int)wd[0], (int)wd[1], (int)wd[2], (int)wd[3]};
       }

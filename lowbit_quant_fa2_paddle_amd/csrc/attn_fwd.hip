@@ -89,40 +89,19 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(AttnPara
   [[maybe_unused]] long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   [[maybe_unused]] bool ts_on = false;
 
-  // ---- which (batch, head, q-block) -----------------------------------------------------------------
-  const unsigned w_id = xcd_remap(blockIdx.x, gridDim.x);
-  int qt = (int)(w_id % (unsigned)p.nQ);
-  const int bh = (int)(w_id / (unsigned)p.nQ);
-  if constexpr (CAUSAL) qt = p.nQ - 1 - qt;  // heaviest q-blocks of a head first
-  const int b = bh / p.Hq, h = bh % p.Hq, hk = h / p.group;
-
-  // ---- extents of this problem: dense batch entry, or sequence b of a packed variable-length batch ----
-  int Sq = p.Sq, Sk = p.Sk, nK = p.nK;
-  int64_t q_off = (int64_t)b * p.qb, k_off = (int64_t)b * p.kb, o_off = (int64_t)b * p.ob;
-  int64_t qsc_base = (int64_t)b * p.qsc_b, ksc_base = (int64_t)b * p.ksc_b;
-  if (p.cu_q != nullptr) {  // attn_qk_int8_block_varlen.py:125-141
-    const int q0 = p.cu_q[b], k0 = p.cu_k[b];
-    // max_seqlen_q / max_seqlen_k (p.Sq / p.Sk) size the grid and the padded scale rows: a sequence longer than the
-    // caller's maximum is cut there, so that every access stays inside the buffers sized from those maxima
-    Sq = min(p.cu_q[b + 1] - q0, p.Sq);
-    Sk = min(p.cu_k[b + 1] - k0, p.Sk);
-    if (qt * 128 >= Sq) return;  // whole workgroup, before any barrier
-    nK = (Sk + 63) >> 6;
-    q_off = (int64_t)q0 * p.qs;
-    k_off = (int64_t)k0 * p.ks;
-    o_off = (int64_t)q0 * p.os;
-    if (p.cu_qscale != nullptr) {
-      qsc_base = (int64_t)p.cu_qscale[b] * p.qsc_b;
-      ksc_base = (int64_t)p.cu_kscale[b] * p.ksc_b;
-    }
-  }
+  // ---- which (q-block, batch, head), and the extents of its problem (attn_common.h) --------------------
+  const WorkItem wi = work_item<CAUSAL>(p);
+  const int qt = wi.qt, b = wi.b, h = wi.h, hk = wi.hk;
+  const Problem pr = locate_problem(p, b, h, qt);
+  if (pr.no_work) return;
+  const int Sq = pr.Sq, Sk = pr.Sk, nK = pr.nK;
 
   const int row0 = qt * 128 + wave * 32;  // first query row of this wave
   const int qrow = row0 + r;
 
   // ---- operand windows (bytes).  The descriptor is re-based per tile with scalar arithmetic, so the
   // hardware range check sees only the loop-invariant per-lane offset.
-  const char* kbase = (const char*)p.k + (k_off + (int64_t)hk * p.kh);
+  const char* kbase = (const char*)p.k + (pr.k_off + (int64_t)hk * p.kh);
   const int64_t k_bytes = (int64_t)(Sk - 1) * p.ks + D;
   const int64_t k_tile_stride = 64 * p.ks;
   const char* vbase = (const char*)p.v + (((int64_t)b * p.Hkv + hk) * nK) * (int64_t)(D * 64);
@@ -145,33 +124,21 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(AttnPara
   static_assert(KROWS * RB == 4096, "one pass of 256 threads x 16 bytes");
   // windows are < 2 GiB (checked by the C ABI): remaining bytes in 32-bit scalar arithmetic
   const int k_bytes32 = (int)k_bytes, v_bytes32 = (int)v_bytes, k_stride32 = (int)k_tile_stride, v_stride32 = (int)v_tile_stride;
-  typedef __attribute__((address_space(3))) void* lds_void_ptr;
   // fetch tile j into LDS buffer `buf_tag`; rows / tiles past the end are outside the descriptor and read as zeros
   auto load_tile = [&](int j, auto buf_tag) __attribute__((always_inline)) {
     constexpr int BUF = decltype(buf_tag)::value;
-    const bool in_range = (unsigned)j < (unsigned)nK;  // the look-ahead past either end gets a window of 0 bytes
-    const int ko = in_range ? j * k_stride32 : 0, vo = in_range ? j * v_stride32 : 0;
-    const int k_rem = in_range ? max(0, k_bytes32 - ko) : 0, v_rem = in_range ? max(0, v_bytes32 - vo) : 0;
-    const __amdgpu_buffer_rsrc_t k_rs = make_rsrc(kbase + ko, (unsigned)k_rem);
-    const __amdgpu_buffer_rsrc_t v_rs = make_rsrc(vbase + vo, (unsigned)v_rem);
-    // DMA destination = wave-uniform base (+ 16 bytes per lane, implicit)
-    char* kdst = smem + BUF * KBYTES + wave * 1024;
-#pragma unroll
-    for (int i = 0; i < KCH; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(k_rs, (lds_void_ptr)(kdst + i * 4096), 16, (int)k_goff, (int)(i * k_gstep), 0, 0);
-    char* vdst = smem + 2 * KBYTES + BUF * VBYTES + wave * 1024;
-#pragma unroll
-    for (int i = 0; i < VCH; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(v_rs, (lds_void_ptr)(vdst + i * 4096), 16, (int)v_goff, (int)(i * 4096), 0, 0);
+    const bool in_range = (unsigned)j < (unsigned)nK;
+    fetch_tile<KCH>(kbase, k_bytes32, k_stride32, j, in_range, smem + BUF * KBYTES + wave * 1024, k_goff, k_gstep);
+    fetch_tile<VCH>(vbase, v_bytes32, v_stride32, j, in_range, smem + 2 * KBYTES + BUF * VBYTES + wave * 1024, v_goff, 4096u);
   };
 
   // processing order of the key tiles: i-th tile processed = tile_of(i)
   constexpr int kRound = 64;
-  const bool rev = !CAUSAL && ((Sk & 63) == 0) && (((qt / kRound) & 1) != 0);  // workgroup-uniform
-  auto tile_of = [&](int i) __attribute__((always_inline)) { return rev ? nK - 1 - i : i; };
+  const bool rev = walks_back<CAUSAL, kRound>(Sk, qt);
+  auto tile_of = [&](int i) __attribute__((always_inline)) { return tile_at(rev, nK, i); };
   load_tile(tile_of(0), std::integral_constant<int, 0>{});  // first K / V tile: in flight while Q is fetched (and quantised)
   // ... and so are the dequantisation scales of the first 64 key tiles (lane l: tile l), needed right after the Q prologue
-  const float* ksc = p.k_scale + ksc_base + (int64_t)hk * p.ksc_h;
+  const float* ksc = p.k_scale + pr.ksc_base + (int64_t)hk * p.ksc_h;
   const int ksc_blk = (int)p.ksc_blk;
   const float ks_first = lane < nK ? ksc[lane * ksc_blk] : 0.f;
 
@@ -184,13 +151,13 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(AttnPara
     // Quantise this workgroup's 128 x D block of Q here instead of in a pre-pass (src/triton/quant_per_block.py:132-178,
     // same arithmetic as quant_per_block_kernel: x * sm_scale -> block amax -> scale = amax / qmax -> RN(x / scale) ->
     // round half away): the lane needs exactly the 16 * KS elements it feeds to the MFMA.
-    const char* qsrc = (const char*)p.q + 2 * (q_off + (int64_t)h * p.qh);
+    const char* qsrc = (const char*)p.q + 2 * (pr.q_off + (int64_t)h * p.qh);
     const __amdgpu_buffer_rsrc_t q_rs = make_rsrc(qsrc, (unsigned)(2 * ((int64_t)(Sq - 1) * p.qs + p.d_valid)));
     float xs[KS][16];
     // q . km in attn_fwd16.hip's order (one value of the correction for every operator and for the backward's pre-pass):
     // this lane's 16 columns of step s are those of lane group g = 2 (s & 1) + hh of a 64-column step there
     float amax = 0.f, dot[2] = {0.f, 0.f};
-    const unsigned short* vec = p.q_dot_vec ? p.q_dot_vec + ((int64_t)b * p.Hkv + hk) * D : nullptr;
+    const unsigned short* vec = p.q_dot_vec ? p.q_dot_vec + ((int64_t)pr.vec_b * p.Hkv + hk) * D : nullptr;
 #pragma unroll
     for (int s = 0; s < KS; ++s)
 #pragma unroll
@@ -198,18 +165,19 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(AttnPara
         const int col = 32 * s + 16 * hh + 8 * hf;
         const u32x4 raw = buf_load16(q_rs, col < p.d_valid ? 2 * ((unsigned)qrow * (unsigned)p.qs + col) : 0x80000000u, 0);
         float xv[8];
+        unpack8<OT>(raw, xv);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          xv[e] = load_cvt<OT>((unsigned short)((e & 1) ? (raw[e >> 1] >> 16) : (raw[e >> 1] & 0xffffu)));
           const float x = xv[e] * p.q_sm_scale;
           xs[s][8 * hf + e] = x;
           amax = fmaxf(amax, fabsf(x));
         }
         if (vec != nullptr) {  // wave-uniform: only when the caller wants the LSE with smooth-K
           const u32x4 vraw = *reinterpret_cast<const u32x4*>(vec + col);
+          float d = dot[s & 1];  // a local: accumulating into dot[s & 1] behind elem16 made the compiler swap the operands of every add
 #pragma unroll
-          for (int e = 0; e < 8; ++e)
-            dot[s & 1] += xv[e] * load_cvt<OT>((unsigned short)((e & 1) ? (vraw[e >> 1] >> 16) : (vraw[e >> 1] & 0xffffu)));
+          for (int e = 0; e < 8; ++e) d += xv[e] * elem16<OT>(vraw, e);
+          dot[s & 1] = d;
         }
       }
     // (S0 + S1) + (S2 + S3), rounded to the storage dtype (src/core.py:294-304)
@@ -218,43 +186,19 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(AttnPara
     float* red = reinterpret_cast<float*>(smem + TILES_BYTES);
     if (lane == 0) red[wave] = amax;
     __syncthreads();
-    amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    amax = amax_collect(red);
     __syncthreads();  // red[] is read by everyone before the overflow vote may reuse it
-    const float scale = fmaxf(amax, 1e-7f) / p.q_qmax;
+    const float scale = block_scale(amax, p.q_qmax);
     qsc = scale;
     const float rcp = 1.0f / scale;
-    const bool exact_rcp_ok = (__builtin_amdgcn_readfirstlane(__float_as_uint(scale)) & 0x7fffffu) != 0x7fffffu;
-    auto encode = [&](auto fast_tag) __attribute__((always_inline)) {  // block-uniform choice, two straight-line instances (as in quant_kernels.hip)
-      constexpr bool FAST = decltype(fast_tag)::value;
+    auto encode = [&](auto fast_tag) __attribute__((always_inline)) {  // block-uniform choice, two straight-line instances
 #pragma unroll
-      for (int s = 0; s < KS; ++s) {
-        unsigned w[4];
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-          int qv[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float xv = xs[s][4 * g4 + e];
-            float y;
-            if constexpr (FAST) {  // Markstein: RN(x / scale) from the correctly rounded reciprocal (see quant_kernels.hip)
-              const float q0 = xv * rcp;
-              y = __builtin_fmaf(__builtin_fmaf(-q0, scale, xv), rcp, q0);
-            } else {
-              y = xv / scale;
-            }
-            qv[e] = (int)(y + __builtin_copysignf(0.5f, y));
-          }
-          const unsigned p01 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pk_i16(qv[0], qv[1]));
-          const unsigned p23 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pk_i16(qv[2], qv[3]));
-          w[g4] = __builtin_amdgcn_perm(p23, p01, 0x06040200u);
-        }
-        qf[s] = i32x4{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
-      }
+      for (int s = 0; s < KS; ++s) qf[s] = quant_codes16<decltype(fast_tag)::value>(xs[s], scale, rcp);
     };
-    if (exact_rcp_ok) encode(std::true_type{});
+    if (markstein_ok(scale)) encode(std::true_type{});
     else encode(std::false_type{});
   } else {
-    const char* qbase = (const char*)p.q + (q_off + (int64_t)h * p.qh);
+    const char* qbase = (const char*)p.q + (pr.q_off + (int64_t)h * p.qh);
     const __amdgpu_buffer_rsrc_t q_rs = make_rsrc(qbase, (unsigned)((int64_t)(Sq - 1) * p.qs + D));
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
@@ -262,7 +206,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(AttnPara
       u32x4 raw = buf_load16(q_rs, (unsigned)qrow * (unsigned)p.qs + col_b, 0);
       qf[s] = __builtin_bit_cast(i32x4, raw);
     }
-    qsc = p.q_scale[qsc_base + (int64_t)h * p.qsc_h + (int64_t)qt * p.qsc_blk];
+    qsc = p.q_scale[pr.qsc_base + (int64_t)h * p.qsc_h + (int64_t)qt * p.qsc_blk];
   }
 
   int n_tiles = nK;
@@ -312,11 +256,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(AttnPara
   // whole output row became NaN (found by tools/soak.py).  A wave therefore leaves the grid - un-rounded scale q_scale k_scale[j],
   // bias taken off the scores with one exact subtraction each, c1 = 8.807 - m - from the start when G >= 2^-6 (kWideG), and from
   // the tile in which one of its row maxima leaves +-2^7 binades (kGridRef) otherwise; 32 VALU more per tile where it applies.
-  float ks_max = ks_first;
-  for (int i = lane + 64; i < nK; i += 64) ks_max = fmaxf(ks_max, ksc[i * ksc_blk]);
-  ks_max = fmaxf(wave_max_nonneg(ks_max), 1e-30f);  // scales are positive (the quantiser floors amax)
-  const float sc_max = qsc * ks_max;
-  const int gexp = __builtin_amdgcn_readfirstlane((int)((__float_as_uint(1.25f * kMagic * sc_max) >> 23) & 0xff) - 127 + 1 - 21);  // log2(G)
+  const int gexp = grid_exponent(qsc * max_k_scale(ksc, ksc_blk, nK, lane, ks_first));  // log2(G)
   const float g = __builtin_ldexpf(1.0f, gexp - 22), invg = __builtin_ldexpf(1.0f, 22 - gexp);
   constexpr int kWideG = -6;            // log2 of the grid step from which every tile dequantises un-rounded
   constexpr float kGridRef = 128.0f;    // |row max| (binades) beyond which a wave leaves the grid (as attn_fwd16.hip)
@@ -331,17 +271,9 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(AttnPara
   // access)
   float sc_tab = 0.f, c0_tab = 0.f, ks_tab = 0.f;
   auto refresh_scale_table = [&](int j0) __attribute__((always_inline)) {
-    const int jt = j0 + lane;
-    const float ks_l = j0 == 0 ? ks_first : (jt < nK ? ksc[jt * ksc_blk] : 0.f);
-    ks_tab = ks_l;
-    // at least one grid step: a block whose scale is < 2^-22 of the largest one (an all-zero K block) must not get
-    // sc = 0, or a masked key (tv = -inf) would turn into fma(-inf, 0, c1) = NaN
-    sc_tab = fmaxf(__builtin_rintf(qsc * ks_l * invg), 1.0f) * g;
-    c0_tab = -kMagic * sc_tab;  // exact
-    if (wide) {
-      sc_tab = fmaxf(qsc * ks_l, 1e-30f);
-      c0_tab = 0.f;
-    }
+    ks_tab = k_scale_of_lane(ksc, ksc_blk, nK, j0, lane, ks_first);
+    sc_tab = tile_scale(qsc, ks_tab, g, invg, wide);
+    c0_tab = wide ? 0.f : -kMagic * sc_tab;  // exact
   };
 
   // One 64-key tile.
@@ -404,7 +336,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(AttnPara
           const float ra = __builtin_fabsf(m_cand);
           if (__any(ra > kGridRef && ra < INFINITY)) {
             wide = true;  // this tile and every later one of the wave (the earlier ones had all their maxima inside the range)
-            sc_tab = fmaxf(qsc * ks_tab, 1e-30f);
+            sc_tab = wide_scale(qsc, ks_tab);
             c0_tab = 0.f;
             sc = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sc_tab), j & 63));
             c0 = 0.f;
@@ -577,7 +509,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(AttnPara
   // ---- epilogue: O = O^T / l x v_scale, LSE ------------------------------------------------------------
   const float inv_l = l_tot > 0.f ? 1.0f / l_tot : 0.f;  // a sequence without keys (packed batches only) yields zeros
   if (qrow < Sq) {
-    unsigned short* op = reinterpret_cast<unsigned short*>(p.o) + o_off + (int64_t)h * p.oh + (int64_t)qrow * p.os;
+    unsigned short* op = reinterpret_cast<unsigned short*>(p.o) + pr.o_off + (int64_t)h * p.oh + (int64_t)qrow * p.os;
 #pragma unroll
     for (int db = 0; db < DB; ++db)
 #pragma unroll
@@ -593,14 +525,8 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd_kernel(AttnPara
         pk.y = (unsigned)store_cvt<OT>(o4[2]) | ((unsigned)store_cvt<OT>(o4[3]) << 16);
         *reinterpret_cast<uint2*>(op + d0) = pk;
       }
-    if (p.lse != nullptr && hh == 0) {
-      float ls = log2f(l_tot) + m_run - kFp8Offset;  // base-2 domain (attn_qk_int8_per_block.py:164-167, qk_int_sv_f8_cuda.cu:689)
-      const int64_t li = ((int64_t)b * p.Hq + h) * p.Sq + qrow;  // dense only (the packed entry points take no lse)
-      ls *= p.lse_scale;
-      if constexpr (QQ) ls += row_corr * p.lse_corr_scale;  // 0 when there is no smoothing vector
-      else if (p.lse_corr != nullptr) ls += p.lse_corr[li] * p.lse_corr_scale;
-      p.lse[li] = ls;
-    }
+    // base-2 domain (attn_qk_int8_per_block.py:164-167, qk_int_sv_f8_cuda.cu:689)
+    if (p.lse != nullptr && hh == 0) store_lse<QQ>(p, pr.lse_base + qrow, log2f(l_tot) + m_run - kFp8Offset, row_corr);
   }
   LBFA8_STAMP(3);
 #if defined(LBFA_STAMPS8)
@@ -617,32 +543,25 @@ hipError_t launch16_attn_fwd_qq_d128(const AttnParams& p, int dtype, int v_dtype
 hipError_t launch16_attn_fwd_f16_d64(const AttnParams& p, int dtype, int causal, hipStream_t stream);
 hipError_t launch16_attn_fwd_f16_d128(const AttnParams& p, int dtype, int causal, hipStream_t stream);
 
-#define LBFA_LAUNCH_FP8(DD, OT, QQ)                                                                    \
-  do {                                                                                                 \
-    if (causal) hipLaunchKernelGGL((attn_fwd_kernel<DD, OT, true, QQ>), grid, block, 0, stream, p);    \
-    else hipLaunchKernelGGL((attn_fwd_kernel<DD, OT, false, QQ>), grid, block, 0, stream, p);          \
-  } while (0)
+template <int D, bool QQ>
+static hipError_t launch_fp8(const AttnParams& p, int o_dtype, int causal, hipStream_t stream) {
+  if (o_dtype == LBFA_F16) return launch_fwd(attn_fwd_kernel<D, LBFA_F16, true, QQ>, attn_fwd_kernel<D, LBFA_F16, false, QQ>, causal, p, stream);
+  return launch_fwd(attn_fwd_kernel<D, LBFA_BF16, true, QQ>, attn_fwd_kernel<D, LBFA_BF16, false, QQ>, causal, p, stream);
+}
 
 // int8 Q / K codes; V fp16 / e4m3 ([D][64]-per-tile image of lbfa_quant_v_fp8)
 hipError_t launch_attn_fwd(const AttnParams& p, int D, int v_dtype, int o_dtype, int causal, hipStream_t stream) {
   if (v_dtype != LBFA_E4M3)
     return D == 64 ? launch16_attn_fwd_d64(p, v_dtype, o_dtype, causal, stream) : launch16_attn_fwd_d128(p, v_dtype, o_dtype, causal, stream);
-  dim3 grid((unsigned)p.B * p.Hq * p.nQ), block(256);
-  if (D == 64) { if (o_dtype == LBFA_F16) LBFA_LAUNCH_FP8(64, LBFA_F16, false); else LBFA_LAUNCH_FP8(64, LBFA_BF16, false); }
-  else { if (o_dtype == LBFA_F16) LBFA_LAUNCH_FP8(128, LBFA_F16, false); else LBFA_LAUNCH_FP8(128, LBFA_BF16, false); }
-  return hipGetLastError();
+  return D == 64 ? launch_fp8<64, false>(p, o_dtype, causal, stream) : launch_fp8<128, false>(p, o_dtype, causal, stream);
 }
 
 // int8 K codes, Q quantised inside the kernel from its fp16 / bf16 source (dtype = Q's = O's); V fp16 or e4m3
 hipError_t launch_attn_fwd_qq(const AttnParams& p, int D, int dtype, int v_dtype, int causal, hipStream_t stream) {
   if (v_dtype != LBFA_E4M3)
     return D == 64 ? launch16_attn_fwd_qq_d64(p, dtype, v_dtype, causal, stream) : launch16_attn_fwd_qq_d128(p, dtype, v_dtype, causal, stream);
-  dim3 grid((unsigned)p.B * p.Hq * p.nQ), block(256);
-  if (D == 64) { if (dtype == LBFA_F16) LBFA_LAUNCH_FP8(64, LBFA_F16, true); else LBFA_LAUNCH_FP8(64, LBFA_BF16, true); }
-  else { if (dtype == LBFA_F16) LBFA_LAUNCH_FP8(128, LBFA_F16, true); else LBFA_LAUNCH_FP8(128, LBFA_BF16, true); }
-  return hipGetLastError();
+  return D == 64 ? launch_fp8<64, true>(p, dtype, causal, stream) : launch_fp8<128, true>(p, dtype, causal, stream);
 }
-#undef LBFA_LAUNCH_FP8
 
 // un-quantised Q / K / V of one dtype
 hipError_t launch_attn_fwd_f16(const AttnParams& p, int D, int dtype, int causal, hipStream_t stream) {

@@ -119,35 +119,12 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd16_kernel(AttnPa
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int i16 = lane & 15, g = lane >> 4;
 
-  // ---- which (batch, head, q-block) -----------------------------------------------------------------
-  const unsigned w_id = xcd_remap(blockIdx.x, gridDim.x);
-  int qt = (int)(w_id % (unsigned)p.nQ);
-  const int bh = (int)(w_id / (unsigned)p.nQ);
-  if constexpr (CAUSAL) qt = p.nQ - 1 - qt;  // heaviest q-blocks of a head first
-  const int b = bh / p.Hq, h = bh % p.Hq, hk = h / p.group;
-
-  int Sq = p.Sq, Sk = p.Sk, nK = p.nK;
-  int64_t q_off = (int64_t)b * p.qb, k_off = (int64_t)b * p.kb, v_off = (int64_t)b * p.vb, o_off = (int64_t)b * p.ob;
-  int64_t qsc_base = (int64_t)b * p.qsc_b, ksc_base = (int64_t)b * p.ksc_b;
-  int64_t lse_base = ((int64_t)b * p.Hq + h) * p.Sq;  // LSE index of query row 0: [B,Hq,Sq]
-  int vec_b = b;                                       // which q_dot_vec set: one per batch entry
-  if (p.cu_q != nullptr) {  // packed variable-length batch (attn_qk_int8_block_varlen.py:125-141); lengths cut at the maxima
-    const int q0 = p.cu_q[b], k0 = p.cu_k[b];
-    lse_base = (int64_t)h * p.lse_hs + q0;  // [Hq, total_q]
-    vec_b = 0;                              // one mean over all packed tokens
-    Sq = min(p.cu_q[b + 1] - q0, p.Sq);
-    Sk = min(p.cu_k[b + 1] - k0, p.Sk);
-    if (qt * 128 >= Sq) return;  // whole workgroup, before any barrier
-    nK = (Sk + 63) >> 6;
-    q_off = (int64_t)q0 * p.qs;
-    k_off = (int64_t)k0 * p.ks;
-    v_off = (int64_t)k0 * p.vs;
-    o_off = (int64_t)q0 * p.os;
-    if (p.cu_qscale != nullptr) {
-      qsc_base = (int64_t)p.cu_qscale[b] * p.qsc_b;
-      ksc_base = (int64_t)p.cu_kscale[b] * p.ksc_b;
-    }
-  }
+  // ---- which (q-block, batch, head), and the extents of its problem (attn_common.h) --------------------
+  const WorkItem wi = work_item<CAUSAL>(p);
+  const int qt = wi.qt, b = wi.b, h = wi.h, hk = wi.hk;
+  const Problem pr = locate_problem(p, b, h, qt);
+  if (pr.no_work) return;
+  const int Sq = pr.Sq, Sk = pr.Sk, nK = pr.nK;
   const int row0 = qt * 128 + wave * 32;  // first query row of this wave
   auto qrow_of = [&](int rb) __attribute__((always_inline)) { return row0 + 16 * rb + i16; };
 
@@ -159,7 +136,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd16_kernel(AttnPa
   {
     constexpr int QESZ = QQ ? 2 : ESZ;  // bytes per element of the Q operand as stored
     const int q_valid = (QQ || QK16) ? p.d_valid : D;
-    const char* qbase = (const char*)p.q + QESZ * (q_off + (int64_t)h * p.qh);
+    const char* qbase = (const char*)p.q + QESZ * (pr.q_off + (int64_t)h * p.qh);
     const __amdgpu_buffer_rsrc_t q_rs = make_rsrc(qbase, (unsigned)(QESZ * ((int64_t)(Sq - 1) * p.qs + q_valid)));
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb)
@@ -174,10 +151,10 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd16_kernel(AttnPa
 
   // ---- operand windows (bytes) ------------------------------------------------------------------------
   const int dq_valid = QK16 ? p.d_valid : D;
-  const char* kbase = (const char*)p.k + ESZ * (k_off + (int64_t)hk * p.kh);
+  const char* kbase = (const char*)p.k + ESZ * (pr.k_off + (int64_t)hk * p.kh);
   const int64_t k_bytes = ESZ * ((int64_t)(Sk - 1) * p.ks + dq_valid);
   const int64_t k_tile_stride = ESZ * 64 * p.ks;
-  const char* vbase = (const char*)p.v + 2 * (v_off + (int64_t)hk * p.vh);
+  const char* vbase = (const char*)p.v + 2 * (pr.v_off + (int64_t)hk * p.vh);
   const int64_t v_bytes = 2 * ((int64_t)(Sk - 1) * p.vs + p.d_valid);
   const int64_t v_tile_stride = 128 * p.vs;
 
@@ -199,31 +176,20 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd16_kernel(AttnPa
   const unsigned v_gstep = 2u * VROWS * (unsigned)p.vs;
   static_assert(KROWS * RB == 4096 && VROWS * 2 * D == 4096, "one pass of 256 threads x 16 bytes");
   const int k_bytes32 = (int)k_bytes, v_bytes32 = (int)v_bytes, k_stride32 = (int)k_tile_stride, v_stride32 = (int)v_tile_stride;
-  typedef __attribute__((address_space(3))) void* lds_void_ptr;
   auto load_tile = [&](int j, auto buf_tag) __attribute__((always_inline)) {
     constexpr int BUF = decltype(buf_tag)::value;
-    const bool in_range = (unsigned)j < (unsigned)nK;  // the look-ahead past either end gets a window of 0 bytes
-    const int ko = in_range ? j * k_stride32 : 0, vo = in_range ? j * v_stride32 : 0;
-    const int k_rem = in_range ? max(0, k_bytes32 - ko) : 0, v_rem = in_range ? max(0, v_bytes32 - vo) : 0;
-    const __amdgpu_buffer_rsrc_t k_rs = make_rsrc(kbase + ko, (unsigned)k_rem);
-    const __amdgpu_buffer_rsrc_t v_rs = make_rsrc(vbase + vo, (unsigned)v_rem);
-    char* kdst = smem + BUF * KBYTES + wave * 1024;  // DMA destination: wave-uniform base (+ 16 bytes per lane, implicit)
-#pragma unroll
-    for (int c = 0; c < KCH; ++c)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(k_rs, (lds_void_ptr)(kdst + c * 4096), 16, (int)k_goff, (int)(c * k_gstep), 0, 0);
-    char* vdst = smem + 2 * KBYTES + BUF * VBYTES + wave * 1024;
-#pragma unroll
-    for (int c = 0; c < VCH; ++c)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(v_rs, (lds_void_ptr)(vdst + c * 4096), 16, (int)v_goff, (int)(c * v_gstep), 0, 0);
+    const bool in_range = (unsigned)j < (unsigned)nK;
+    fetch_tile<KCH>(kbase, k_bytes32, k_stride32, j, in_range, smem + BUF * KBYTES + wave * 1024, k_goff, k_gstep);
+    fetch_tile<VCH>(vbase, v_bytes32, v_stride32, j, in_range, smem + 2 * KBYTES + BUF * VBYTES + wave * 1024, v_goff, v_gstep);
   };
 
   // processing order of the key tiles (ping-pong per round of Q blocks, see attn_fwd.hip)
   constexpr int kRound = (D == 64) ? 96 : 64;
-  const bool rev = !CAUSAL && kPingPong && ((Sk & 63) == 0) && (((qt / kRound) & 1) != 0);
-  auto tile_of = [&](int i) __attribute__((always_inline)) { return rev ? nK - 1 - i : i; };
+  const bool rev = kPingPong && walks_back<CAUSAL, kRound>(Sk, qt);
+  auto tile_of = [&](int i) __attribute__((always_inline)) { return tile_at(rev, nK, i); };
   load_tile(tile_of(0), std::integral_constant<int, 0>{});
   const float* ksc = nullptr;
-  if constexpr (!QK16) ksc = p.k_scale + ksc_base + (int64_t)hk * p.ksc_h;
+  if constexpr (!QK16) ksc = p.k_scale + pr.ksc_base + (int64_t)hk * p.ksc_h;
   const int ksc_blk = (int)p.ksc_blk;
   float ks_first = 0.f;
   if constexpr (!QK16) ks_first = lane < nK ? ksc[lane * ksc_blk] : 0.f;
@@ -236,7 +202,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd16_kernel(AttnPa
     // in-kernel Q quantiser: same arithmetic as quant_per_block_kernel (src/triton/quant_per_block.py:132-178)
     float xs[2][KS][16];
     float amax = 0.f;
-    const unsigned short* vec = p.q_dot_vec ? p.q_dot_vec + ((int64_t)vec_b * p.Hkv + hk) * D : nullptr;
+    const unsigned short* vec = p.q_dot_vec ? p.q_dot_vec + ((int64_t)pr.vec_b * p.Hkv + hk) * D : nullptr;
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb) {
       float dot = 0.f;
@@ -245,11 +211,10 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd16_kernel(AttnPa
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
           const int col = 64 * s + 16 * g + 8 * hf;
-          const u32x4 raw = qraw[rb][s][hf];
           float xv[8];
+          unpack8<OT>(qraw[rb][s][hf], xv);
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
-            xv[e] = load_cvt<OT>((unsigned short)((e & 1) ? (raw[e >> 1] >> 16) : (raw[e >> 1] & 0xffffu)));
             const float x = xv[e] * p.q_sm_scale;
             xs[rb][s][8 * hf + e] = x;
             amax = fmaxf(amax, fabsf(x));
@@ -257,8 +222,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd16_kernel(AttnPa
           if (vec != nullptr) {
             const u32x4 vraw = *reinterpret_cast<const u32x4*>(vec + col);
 #pragma unroll
-            for (int e = 0; e < 8; ++e)
-              dot += xv[e] * load_cvt<OT>((unsigned short)((e & 1) ? (vraw[e >> 1] >> 16) : (vraw[e >> 1] & 0xffffu)));
+            for (int e = 0; e < 8; ++e) dot += xv[e] * elem16<OT>(vraw, e);
           }
         }
       row_corr[rb] = load_cvt<OT>(store_cvt<OT>(rows4_sum(dot)));  // rounded to the storage dtype (src/core.py:294-304)
@@ -268,50 +232,26 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd16_kernel(AttnPa
     float* red = reinterpret_cast<float*>(smem + TILES_BYTES);
     if (lane == 0) red[wave] = amax;
     __syncthreads();
-    amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    amax = amax_collect(red);
     __syncthreads();
     LBFA_STAMP(7);
-    const float scale = fmaxf(amax, 1e-7f) / p.q_qmax;
+    const float scale = block_scale(amax, p.q_qmax);
     qsc = scale;
     const float rcp = 1.0f / scale;
-    const bool exact_rcp_ok = (__builtin_amdgcn_readfirstlane(__float_as_uint(scale)) & 0x7fffffu) != 0x7fffffu;
-    auto encode = [&](auto fast_tag) __attribute__((always_inline)) {
-      constexpr bool FAST = decltype(fast_tag)::value;
+    auto encode = [&](auto fast_tag) __attribute__((always_inline)) {  // block-uniform choice, two straight-line instances
 #pragma unroll
       for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
-        for (int s = 0; s < KS; ++s) {
-          unsigned w[4];
-#pragma unroll
-          for (int g4 = 0; g4 < 4; ++g4) {
-            int qv[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float xv = xs[rb][s][4 * g4 + e];
-              float y;
-              if constexpr (FAST) {
-                const float q0 = xv * rcp;
-                y = __builtin_fmaf(__builtin_fmaf(-q0, scale, xv), rcp, q0);
-              } else {
-                y = xv / scale;
-              }
-              qv[e] = (int)(y + __builtin_copysignf(0.5f, y));
-            }
-            const unsigned p01 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pk_i16(qv[0], qv[1]));
-            const unsigned p23 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pk_i16(qv[2], qv[3]));
-            w[g4] = __builtin_amdgcn_perm(p23, p01, 0x06040200u);
-          }
-          qf[rb][s] = i32x4{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
-        }
+        for (int s = 0; s < KS; ++s) qf[rb][s] = quant_codes16<decltype(fast_tag)::value>(xs[rb][s], scale, rcp);
     };
-    if (exact_rcp_ok) encode(std::true_type{});
+    if (markstein_ok(scale)) encode(std::true_type{});
     else encode(std::false_type{});
   } else {
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
       for (int s = 0; s < KS; ++s) qf[rb][s] = __builtin_bit_cast(i32x4, qraw[rb][s][0]);
-    if constexpr (!QK16) qsc = p.q_scale[qsc_base + (int64_t)h * p.qsc_h + (int64_t)qt * p.qsc_blk];
+    if constexpr (!QK16) qsc = p.q_scale[pr.qsc_base + (int64_t)h * p.qsc_h + (int64_t)qt * p.qsc_blk];
   }
 
   LBFA_STAMP(1);
@@ -366,19 +306,14 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd16_kernel(AttnPa
 
   // ---- exact bias folding (see attn_fwd.hip): constants on a common power-of-two grid ------------------------------
   float ks_max = 0.f;
-  if constexpr (!QK16) {
-    ks_max = ks_first;
-    for (int i = lane + 64; i < nK; i += 64) ks_max = fmaxf(ks_max, ksc[i * ksc_blk]);
-    ks_max = fmaxf(wave_max_nonneg(ks_max), 1e-30f);
-  }
+  if constexpr (!QK16) ks_max = max_k_scale(ksc, ksc_blk, nK, lane, ks_first);
   // wave-uniform values below are moved to SGPRs by hand (the compiler keeps uniform floats in VGPRs, and the tile loop has none
   // to spare: left alone, the QQ instances parked 14 cold dwords in scratch)
   auto uniform = [](float v) __attribute__((always_inline)) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
   };
   qsc = uniform(qsc);
-  const float sc_max = qsc * ks_max;
-  const int gexp = __builtin_amdgcn_readfirstlane((int)((__float_as_uint(1.25f * kMagic * sc_max) >> 23) & 0xff) - 127 + 1 - 21);  // log2(G)
+  const int gexp = grid_exponent(qsc * ks_max);  // log2(G)
   const float G = uniform(__builtin_ldexpf(1.0f, gexp)), invG = uniform(__builtin_ldexpf(1.0f, -gexp));
   const float gg = uniform(__builtin_ldexpf(1.0f, gexp - 22)), invg = uniform(__builtin_ldexpf(1.0f, 22 - gexp));
   // Wide scores: the grid is one integer step of a score wide at best (G in (7.5, 15] sc_max), and a reference rounded up to it puts
@@ -397,11 +332,8 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd16_kernel(AttnPa
   float sc_tab = 0.f, ks_tab = 0.f;
   auto refresh_scale_table = [&](int j0) __attribute__((always_inline)) {
     if constexpr (!QK16) {
-      const int jt = j0 + lane;
-      const float ks_l = j0 == 0 ? ks_first : (jt < nK ? ksc[jt * ksc_blk] : 0.f);
-      ks_tab = ks_l;
-      sc_tab = fmaxf(__builtin_rintf(qsc * ks_l * invg), 1.0f) * gg;  // >= one grid step: a masked key must not meet sc = 0
-      if (wide) sc_tab = fmaxf(qsc * ks_l, 1e-30f);
+      ks_tab = k_scale_of_lane(ksc, ksc_blk, nK, j0, lane, ks_first);
+      sc_tab = tile_scale(qsc, ks_tab, gg, invg, wide);
     }
   };
 
@@ -576,7 +508,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd16_kernel(AttnPa
               // this tile and every later one of the wave: un-rounded scale, bias subtracted exactly (below).  Rare; only the tile
               // bodies of the replay carry this code, and it touches no memory: the table is rebuilt from the raw k_scales it keeps
               wide = true;
-              sc_tab = fmaxf(qsc * ks_tab, 1e-30f);
+              sc_tab = wide_scale(qsc, ks_tab);
               sc = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sc_tab), j & 63));
               c0 = 0.f;
             }
@@ -755,7 +687,7 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd16_kernel(AttnPa
     const int qrow = qrow_of(rb);
     const float inv_l = l_tot[rb] > 0.f ? 1.0f / l_tot[rb] : 0.f;
     if (qrow < Sq) {
-      unsigned short* op = reinterpret_cast<unsigned short*>(p.o) + o_off + (int64_t)h * p.oh + (int64_t)qrow * p.os;
+      unsigned short* op = reinterpret_cast<unsigned short*>(p.o) + pr.o_off + (int64_t)h * p.oh + (int64_t)qrow * p.os;
 #pragma unroll
       for (int cb = 0; cb < CB; ++cb) {
         const int d0 = 16 * cb + 4 * g;
@@ -765,14 +697,8 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd16_kernel(AttnPa
         pk.y = (unsigned)store_cvt<OT>(acc_o[rb][cb][2] * inv_l) | ((unsigned)store_cvt<OT>(acc_o[rb][cb][3] * inv_l) << 16);
         *reinterpret_cast<uint2*>(op + d0) = pk;
       }
-      if (p.lse != nullptr && g == 0) {
-        float ls = log2f(l_tot[rb]) + m_run[rb];  // base-2 domain (attn_qk_int8_per_block.py:164-167)
-        const int64_t li = lse_base + qrow;
-        ls *= p.lse_scale;
-        if constexpr (QQ) ls += row_corr[rb] * p.lse_corr_scale;
-        else if (p.lse_corr != nullptr) ls += p.lse_corr[li] * p.lse_corr_scale;
-        p.lse[li] = ls;
-      }
+      // base-2 domain (attn_qk_int8_per_block.py:164-167)
+      if (p.lse != nullptr && g == 0) store_lse<QQ>(p, pr.lse_base + qrow, log2f(l_tot[rb]) + m_run[rb], row_corr[rb]);
     }
   }
   LBFA_STAMP(5);
@@ -792,48 +718,26 @@ __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void attn_fwd16_kernel(AttnPa
 #define LBFA_CAT(a, b) LBFA_CAT2(a, b)
 #define LBFA_DNAME(fn) LBFA_CAT(fn, LBFA_D16)
 
+template <int QT, int VT, int OT, bool QQ>
+static hipError_t launch16(const AttnParams& p, int causal, hipStream_t stream) {
+  return launch_fwd(attn_fwd16_kernel<LBFA_D16, QT, VT, OT, true, QQ>, attn_fwd16_kernel<LBFA_D16, QT, VT, OT, false, QQ>, causal, p, stream);
+}
+
 // int8 Q and K codes, fp16 V (lbfa_attn_fwd: bf16 V is cast by the caller, as src/core.py:307-308 does before its kernel call)
 hipError_t LBFA_DNAME(launch16_attn_fwd_d)(const AttnParams& p, int v_dtype, int o_dtype, int causal, hipStream_t stream) {
   if (v_dtype != LBFA_F16) return hipErrorInvalidValue;
-  dim3 grid((unsigned)p.B * p.Hq * p.nQ), block(256);
-#define LBFA_A(OT)                                                                                                    \
-  do {                                                                                                                \
-    if (causal) hipLaunchKernelGGL((attn_fwd16_kernel<LBFA_D16, kQInt8, LBFA_F16, OT, true>), grid, block, 0, stream, p);  \
-    else hipLaunchKernelGGL((attn_fwd16_kernel<LBFA_D16, kQInt8, LBFA_F16, OT, false>), grid, block, 0, stream, p);        \
-  } while (0)
-  if (o_dtype == LBFA_F16) LBFA_A(LBFA_F16);
-  else LBFA_A(LBFA_BF16);
-#undef LBFA_A
-  return hipGetLastError();
+  return o_dtype == LBFA_F16 ? launch16<kQInt8, LBFA_F16, LBFA_F16, false>(p, causal, stream) : launch16<kQInt8, LBFA_F16, LBFA_BF16, false>(p, causal, stream);
 }
 
 // Q quantised in the kernel from its fp16 / bf16 source (dtype, also O's); V fp16 (the one-call operators cast a bf16 V in a
 // pre-pass: converting it on the way into LDS cost the kernel 9..10 % and 25..56 spilled registers)
 hipError_t LBFA_DNAME(launch16_attn_fwd_qq_d)(const AttnParams& p, int dtype, int v_dtype, int causal, hipStream_t stream) {
   if (v_dtype != LBFA_F16) return hipErrorInvalidValue;
-  dim3 grid((unsigned)p.B * p.Hq * p.nQ), block(256);
-#define LBFA_QQ(DT)                                                                                                          \
-  do {                                                                                                                       \
-    if (causal) hipLaunchKernelGGL((attn_fwd16_kernel<LBFA_D16, kQInt8, LBFA_F16, DT, true, true>), grid, block, 0, stream, p); \
-    else hipLaunchKernelGGL((attn_fwd16_kernel<LBFA_D16, kQInt8, LBFA_F16, DT, false, true>), grid, block, 0, stream, p);       \
-  } while (0)
-  if (dtype == LBFA_F16) LBFA_QQ(LBFA_F16);
-  else LBFA_QQ(LBFA_BF16);
-#undef LBFA_QQ
-  return hipGetLastError();
+  return dtype == LBFA_F16 ? launch16<kQInt8, LBFA_F16, LBFA_F16, true>(p, causal, stream) : launch16<kQInt8, LBFA_F16, LBFA_BF16, true>(p, causal, stream);
 }
 
 hipError_t LBFA_DNAME(launch16_attn_fwd_f16_d)(const AttnParams& p, int dtype, int causal, hipStream_t stream) {
-  dim3 grid((unsigned)p.B * p.Hq * p.nQ), block(256);
-#define LBFA_F(DT)                                                                                             \
-  do {                                                                                                         \
-    if (causal) hipLaunchKernelGGL((attn_fwd16_kernel<LBFA_D16, DT, DT, DT, true>), grid, block, 0, stream, p);   \
-    else hipLaunchKernelGGL((attn_fwd16_kernel<LBFA_D16, DT, DT, DT, false>), grid, block, 0, stream, p);         \
-  } while (0)
-  if (dtype == LBFA_F16) LBFA_F(LBFA_F16);
-  else LBFA_F(LBFA_BF16);
-#undef LBFA_F
-  return hipGetLastError();
+  return dtype == LBFA_F16 ? launch16<LBFA_F16, LBFA_F16, LBFA_F16, false>(p, causal, stream) : launch16<LBFA_BF16, LBFA_BF16, LBFA_BF16, false>(p, causal, stream);
 }
 
 }  // namespace lbfa

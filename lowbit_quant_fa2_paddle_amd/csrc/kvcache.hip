@@ -17,16 +17,6 @@
 
 namespace lbfa {
 
-template <int DT>
-__device__ __forceinline__ void unpack8k(const uint4& raw, float (&v)[8]) {
-  const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = load_cvt<DT>((unsigned short)(w[i] & 0xffffu));
-    v[2 * i + 1] = load_cvt<DT>((unsigned short)(w[i] >> 16));
-  }
-}
-
 // lengths of one sequence, clipped so that nothing is written past the capacity
 __device__ __forceinline__ void append_range(const AppendParams& p, int b, int& s0, int& tb) {
   s0 = min(max(p.seqlens[b], 0), p.cap);
@@ -57,7 +47,7 @@ __global__ __launch_bounds__(256) void kvcache_append_kernel(AppendParams p) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) mean[i] = 0.f;
   const bool has_mean = p.km != nullptr;
-  if (has_mean) unpack8k<DT>(*reinterpret_cast<const uint4*>(p.km + bh * D + c * 8), mean);
+  if (has_mean) unpack8<DT>(*reinterpret_cast<const uint4*>(p.km + bh * D + c * 8), mean);
   const int end = s0 + tb;
 
   // x = 0: block `first`, then block `last` when it is another one; x >= 1: one middle block
@@ -79,7 +69,7 @@ __global__ __launch_bounds__(256) void kvcache_append_kernel(AppendParams p) {
     for (int ps = 0; ps < NP; ++ps) {
       const int row = r0 + ps * RPP + rl;
       float v[8];
-      unpack8k<DT>(raw[ps], v);
+      unpack8<DT>(raw[ps], v);
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         float xv = v[i];
@@ -92,8 +82,7 @@ __global__ __launch_bounds__(256) void kvcache_append_kernel(AppendParams p) {
     amax = wave_max_nonneg(amax);
     if ((t & 63) == 0) wmax[t >> 6] = amax;
     __syncthreads();  // also: every read of k_tail (pass 0) is done before pass 1 stores to it
-    const float am = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-    const float scale = fmaxf(am, 1e-7f) / p.qmax;
+    const float scale = block_scale(amax_collect(wmax), p.qmax);
     if (t == 0) p.k_scale[bh * (p.cap >> 6) + blk] = scale;
     const bool open = (blk == last) && (end & 63) != 0;  // this block is the open one afterwards: keep its raw rows
 #pragma unroll
@@ -101,30 +90,13 @@ __global__ __launch_bounds__(256) void kvcache_append_kernel(AppendParams p) {
       const int row = r0 + ps * RPP + rl;
       int q[8];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float y = xs[ps][i] / scale;  // correctly rounded quotient, as the quantiser's
-        q[i] = (int)(y + __builtin_copysignf(0.5f, y));
-      }
-      const unsigned p01 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pk_i16(q[0], q[1]));
-      const unsigned p23 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pk_i16(q[2], q[3]));
-      const unsigned p45 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pk_i16(q[4], q[5]));
-      const unsigned p67 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pk_i16(q[6], q[7]));
-      const unsigned w0 = __builtin_amdgcn_perm(p23, p01, 0x06040200u);
-      const unsigned w1 = __builtin_amdgcn_perm(p67, p45, 0x06040200u);
-      if (row < end) *reinterpret_cast<uint2*>(codes + (int64_t)row * D) = make_uint2(w0, w1);
+      for (int i = 0; i < 8; ++i) q[i] = quant_code<false>(xs[ps][i], scale, 0.f);  // the plain division
+      if (row < end) *reinterpret_cast<uint2*>(codes + (int64_t)row * D) = pack8_i8(q);
       if (row >= s0 && row < end) {
         if (open) *reinterpret_cast<uint4*>(tail + (int64_t)(row - r0) * D) = raw[ps];
-        uint4 vr = *reinterpret_cast<const uint4*>(vnew + (int64_t)(row - s0) * p.vs);
-        if constexpr (DT == LBFA_BF16) {
-          unsigned w[4] = {vr.x, vr.y, vr.z, vr.w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const f16x2 pk = f16x2{(_Float16)__uint_as_float(w[e] << 16), (_Float16)__uint_as_float(w[e] & 0xffff0000u)};
-            w[e] = __builtin_bit_cast(unsigned, pk);
-          }
-          vr = make_uint4(w[0], w[1], w[2], w[3]);
-        }
-        *reinterpret_cast<uint4*>(vdst + (int64_t)row * D) = vr;
+        u32x4 vr = *reinterpret_cast<const u32x4*>(vnew + (int64_t)(row - s0) * p.vs);
+        if constexpr (DT == LBFA_BF16) vr = bf16x8_to_f16x8(vr);
+        *reinterpret_cast<u32x4*>(vdst + (int64_t)row * D) = vr;
       }
     }
     __syncthreads();  // wmax is reused by the second pass
@@ -148,7 +120,7 @@ __global__ __launch_bounds__(256) void kvcache_mean_kernel(RaggedMeanParams p) {
   for (int i = 0; i < 8; ++i) acc[i] = 0.0;
   for (int r = rl; r < n; r += RL) {
     float v[8];
-    unpack8k<DT>(*reinterpret_cast<const uint4*>(base + (int64_t)r * p.ks), v);
+    unpack8<DT>(*reinterpret_cast<const uint4*>(base + (int64_t)r * p.ks), v);
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc[i] += (double)v[i];
   }

@@ -74,6 +74,89 @@ __device__ __forceinline__ float wave_max_nonneg(float v) {
   return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(v), 63));
 }
 
+// ---- the int8 block quantiser's arithmetic: the one statement that quant_per_block_kernel, the KV-cache append, the decode
+// kernel and the in-kernel Q quantisers of the forward kernels share (their codes and scales agree bit for bit) -----------------
+// A 16-byte chunk (uint4 or u32x4) = 8 elements of the storage dtype: unpack8 converts all eight; elem16 converts element e, for
+// the loops that consume each element as it is converted (the q . km dot products, the V encoder) - unpacking the whole chunk
+// in front of them re-orders their instruction streams
+template <int DT, typename Chunk>
+__device__ __forceinline__ float elem16(Chunk raw, int e) {
+  const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
+  return load_cvt<DT>((unsigned short)((e & 1) ? (w[e >> 1] >> 16) : (w[e >> 1] & 0xffffu)));
+}
+template <int DT, typename Chunk>
+__device__ __forceinline__ void unpack8(const Chunk& raw, float (&v)[8]) {
+  const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    v[2 * i] = load_cvt<DT>((unsigned short)(w[i] & 0xffffu));
+    v[2 * i + 1] = load_cvt<DT>((unsigned short)(w[i] >> 16));
+  }
+}
+// bf16 pairs -> fp16 pairs, in place (a 16-byte chunk = 8 elements)
+__device__ __forceinline__ u32x4 bf16x8_to_f16x8(u32x4 val) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float lo = __uint_as_float(val[e] << 16), hi = __uint_as_float(val[e] & 0xffff0000u);
+    const f16x2 pk = f16x2{(_Float16)lo, (_Float16)hi};
+    val[e] = __builtin_bit_cast(unsigned, pk);
+  }
+  return val;
+}
+// workgroup amax of four waves from the four LDS floats they posted their maxima to; the barriers are the caller's
+__device__ __forceinline__ float amax_collect(const float* w4) { return fmaxf(fmaxf(w4[0], w4[1]), fmaxf(w4[2], w4[3])); }
+
+__device__ __forceinline__ float block_scale(float amax, float qmax) { return fmaxf(amax, 1e-7f) / qmax; }
+// y = x / scale must be the correctly rounded fp32 quotient (the codes are bit-exact against the oracle).  A full IEEE division
+// per element costs ~12 VALU ops; the divisor is the same for the whole block, so FAST uses Markstein's sequence with the
+// correctly rounded reciprocal rcp = 1 / scale: q0 = x*r, e = fma(-q0, s, x) (exact), q1 = fma(e, r, q0) == RN(x/s) for every
+// x unless the significand of s is all ones (checked on 1.2e8 adversarial samples; theorem: Markstein 1990), in which case the
+// plain division is used: markstein_ok(scale) picks, block-uniform, between two straight-line instances of the encode loop.
+__device__ __forceinline__ bool markstein_ok(float scale) {
+  return (__builtin_amdgcn_readfirstlane(__float_as_uint(scale)) & 0x7fffffu) != 0x7fffffu;
+}
+template <bool FAST>
+__device__ __forceinline__ int quant_code(float x, float scale, float rcp) {
+  float y;
+  if constexpr (FAST) {
+    const float q0 = x * rcp;
+    y = __builtin_fmaf(__builtin_fmaf(-q0, scale, x), rcp, q0);
+  } else {
+    y = x / scale;
+  }
+  // round half away from zero (src/triton/quant_per_block.py:174-176): y + 0.5*sign(y), then truncate (v_cvt_i32_f32 truncates)
+  return (int)(y + __builtin_copysignf(0.5f, y));
+}
+// |q| <= 127: v_cvt_pk_i16_i32 keeps the low bytes, v_perm_b32 gathers bytes 0 and 2 of each pair
+__device__ __forceinline__ unsigned pack4_i8(const int* q) {
+  const unsigned p01 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pk_i16(q[0], q[1]));
+  const unsigned p23 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pk_i16(q[2], q[3]));
+  return __builtin_amdgcn_perm(p23, p01, 0x06040200u);
+}
+// (pairs taken from the top down: the order in which the compiler laid out the spelled-out pack of the row quantisers, whose
+// stores sit in a conditional block; the straight-line sites use pack4_i8)
+__device__ __forceinline__ uint2 pack8_i8(const int (&q)[8]) {
+  const unsigned p67 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pk_i16(q[6], q[7]));
+  const unsigned p45 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pk_i16(q[4], q[5]));
+  const unsigned hi = __builtin_amdgcn_perm(p67, p45, 0x06040200u);
+  const unsigned p23 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pk_i16(q[2], q[3]));
+  const unsigned p01 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pk_i16(q[0], q[1]));
+  return make_uint2(__builtin_amdgcn_perm(p23, p01, 0x06040200u), hi);
+}
+// 16 consecutive elements of a row -> their 16 codes, as the int8 MFMAs take them (one operand of 16 bytes per lane)
+template <bool FAST>
+__device__ __forceinline__ i32x4 quant_codes16(const float (&x)[16], float scale, float rcp) {
+  unsigned w[4];
+#pragma unroll
+  for (int g4 = 0; g4 < 4; ++g4) {
+    int q[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) q[e] = quant_code<FAST>(x[4 * g4 + e], scale, rcp);
+    w[g4] = pack4_i8(q);
+  }
+  return i32x4{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
+}
+
 // XCD-aware bijective remap of a 1-D grid: hardware deals consecutive workgroup ids round-robin over
 // the 8 XCDs, so ids {x, x+8, x+16, ...} share one L2.  Give each such residue class a CONTIGUOUS
 // chunk of the logical work list, so that neighbours in the work list (same (batch, kv-head): same

@@ -95,16 +95,6 @@ __global__ void mean_finalize_kernel(MeanParams p) {
 // per-block int8 / int4-range quantiser
 // ---------------------------------------------------------------------------------------------------
 
-template <int DT>
-__device__ __forceinline__ void unpack8(const uint4& raw, float (&v)[8]) {
-  const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = load_cvt<DT>((unsigned short)(w[i] & 0xffffu));
-    v[2 * i + 1] = load_cvt<DT>((unsigned short)(w[i] >> 16));
-  }
-}
-
 // NB = consecutive blocks of BLK rows handled by one workgroup (all their rows are requested before any arithmetic; the
 // mean / dot vectors and the fused last step of the mean are fetched once for all of them).
 template <int DT, int D, int BLK, bool HAS_MEAN, bool HAS_DOT, int NB = 1>
@@ -210,51 +200,24 @@ __global__ __launch_bounds__(256) void quant_per_block_kernel(QuantParams p) {
   }
   __syncthreads();
 
-  // y = xs / scale must be the correctly rounded fp32 quotient (the codes are bit-exact against the oracle).
-  // A full IEEE division per element costs ~12 VALU ops; the divisor is the same for the whole block, so use
-  // Markstein's sequence with the correctly rounded reciprocal: q0 = x*r, e = fma(-q0, s, x) (exact),
-  // q1 = fma(e, r, q0) == RN(x/s) for every x unless the significand of s is all ones (checked on 1.2e8
-  // adversarial samples; theorem: Markstein 1990), in which case the plain division is used.
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
     const int blk = blk0 + nb;
     if (blk * BLK >= S) break;  // workgroup-uniform: a block past the end of the sequence owns no scale slot
-    const float am = fmaxf(fmaxf(wmax[nb][0], wmax[nb][1]), fmaxf(wmax[nb][2], wmax[nb][3]));
-    const float scale = fmaxf(am, 1e-7f) / p.qmax;
+    const float scale = block_scale(amax_collect(wmax[nb]), p.qmax);
     if (t == 0) p.scale[sbase + (int64_t)h * p.scale_h + (int64_t)blk * p.scale_blk] = scale;
     const float rcp = 1.0f / scale;
-    const bool exact_rcp_ok =
-        (__builtin_amdgcn_readfirstlane(__float_as_uint(scale)) & 0x7fffffu) != 0x7fffffu;  // block-uniform
     auto encode = [&](auto fast_tag) {
-      constexpr bool FAST = decltype(fast_tag)::value;
 #pragma unroll
       for (int ps = 0; ps < NP; ++ps) {
         const int row = blk * BLK + ps * RPP + rl;
         int q[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float xv = xs[nb][ps][i];
-          float y;
-          if constexpr (FAST) {
-            const float q0 = xv * rcp;
-            y = __builtin_fmaf(__builtin_fmaf(-q0, scale, xv), rcp, q0);
-          } else {
-            y = xv / scale;
-          }
-          // round half away from zero (:174-176): y + 0.5*sign(y), then truncate (v_cvt_i32_f32 truncates)
-          q[i] = (int)(y + __builtin_copysignf(0.5f, y));
-        }
-        // |q| <= 127: v_cvt_pk_i16_i32 keeps the low bytes, v_perm_b32 gathers bytes 0 and 2 of each pair
-        const unsigned p01 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pk_i16(q[0], q[1]));
-        const unsigned p23 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pk_i16(q[2], q[3]));
-        const unsigned p45 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pk_i16(q[4], q[5]));
-        const unsigned p67 = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pk_i16(q[6], q[7]));
-        const unsigned w0 = __builtin_amdgcn_perm(p23, p01, 0x06040200u);
-        const unsigned w1 = __builtin_amdgcn_perm(p67, p45, 0x06040200u);
-        if (row < S) *reinterpret_cast<uint2*>(obase + (int64_t)row * p.os) = make_uint2(w0, w1);
+        for (int i = 0; i < 8; ++i) q[i] = quant_code<decltype(fast_tag)::value>(xs[nb][ps][i], scale, rcp);
+        if (row < S) *reinterpret_cast<uint2*>(obase + (int64_t)row * p.os) = pack8_i8(q);
       }
     };
-    if (exact_rcp_ok) encode(std::true_type{});
+    if (markstein_ok(scale)) encode(std::true_type{});
     else encode(std::false_type{});
   }
 }
@@ -306,13 +269,10 @@ __global__ __launch_bounds__(256) void v_amax_kernel(VFp8Params p) {
   for (int i = 0; i < 8; ++i) am[i] = 0.f;
   if (c * 8 < p.d_valid)
   for (int r = r0 + rl; r < r1; r += RL) {
-    const uint4 raw = *reinterpret_cast<const uint4*>(base + (int64_t)r * p.vs);
-    const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
+    float v[8];
+    unpack8<DT>(*reinterpret_cast<const uint4*>(base + (int64_t)r * p.vs), v);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      am[2 * i] = fmaxf(am[2 * i], fabsf(load_cvt<DT>((unsigned short)(w[i] & 0xffffu))));
-      am[2 * i + 1] = fmaxf(am[2 * i + 1], fabsf(load_cvt<DT>((unsigned short)(w[i] >> 16))));
-    }
+    for (int i = 0; i < 8; ++i) am[i] = fmaxf(am[i], fabsf(v[i]));
   }
 #pragma unroll
   for (int i = 0; i < 8; ++i) red[rl][c * 8 + i] = am[i];
@@ -346,11 +306,10 @@ __global__ __launch_bounds__(256) void v_encode_kernel(VFp8Params p) {
     const int row = tl * 64 + key;
     uint4 raw = make_uint4(0, 0, 0, 0);
     if (row < p.S && c * 8 < p.d_valid) raw = *reinterpret_cast<const uint4*>(base + (int64_t)row * p.vs);
-    const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
     const int pos = vfp8_pos_of_key(key);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      const float v = load_cvt<DT>((unsigned short)((i & 1) ? (w[i >> 1] >> 16) : (w[i >> 1] & 0xffffu))) * inv[i];
+      const float v = elem16<DT>(raw, i) * inv[i];
       // v_cvt_pk_fp8_f32: OCP e4m3fn on gfx950, RNE, saturating
       const unsigned pk = __builtin_amdgcn_cvt_pk_fp8_f32(v, 0.f, 0u, false);
       // 16-byte chunk XOR-swizzled by the channel so the attention kernel's ds_read_b128 of 16 channels x one
@@ -384,14 +343,8 @@ __global__ __launch_bounds__(256) void cast_bf16_f16_kernel(CastParams p) {
     const int s = (int)(r % p.S);
     r /= p.S;
     const int h = (int)(r % p.H), b = (int)(r / p.H);
-    const uint4 raw = *reinterpret_cast<const uint4*>(p.src + b * p.sb + h * p.sh + s * p.ss + c * 8);
-    unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const f16x2 pk = f16x2{(_Float16)__uint_as_float(w[e] << 16), (_Float16)__uint_as_float(w[e] & 0xffff0000u)};
-      w[e] = __builtin_bit_cast(unsigned, pk);
-    }
-    *reinterpret_cast<uint4*>(p.dst + b * p.db + h * p.dh + s * p.ds + c * 8) = make_uint4(w[0], w[1], w[2], w[3]);
+    const u32x4 raw = *reinterpret_cast<const u32x4*>(p.src + b * p.sb + h * p.sh + s * p.ss + c * 8);
+    *reinterpret_cast<u32x4*>(p.dst + b * p.db + h * p.dh + s * p.ds + c * 8) = bf16x8_to_f16x8(raw);
   }
 }
 
