@@ -393,6 +393,49 @@ int lbfa_decode(const void* q, int dtype, const int8_t* k_codes, const float* k_
                 int B, int Hq, int Hkv, int Sq, int D, int capacity, int max_seqlen_k, int num_splits,
                 const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream);
 
+/*
+ * The same cache as a POOL OF PAGES behind one block table per sequence (additive to ABI 200, LBFA_VERSION unchanged: look the
+ * symbols up).  All tensors contiguous and caller-owned; page_size a positive multiple of 64, D in {64, 128}:
+ *   k_codes     int8  [num_pages, Hkv, page_size, D]         codes of K - km
+ *   k_scale     fp32  [num_pages, Hkv, page_size / 64]       one scale per 64 keys
+ *   v_cache     fp16  [num_pages, Hkv, page_size, D]         V
+ *   block_table int32 [num_slots, max_pages_per_seq], device pages of each sequence; entries past a sequence's last page are
+ *                                                            never read
+ *   k_tail      [num_slots, Hkv, 64, D] storage dtype        raw rows of the open 64-key block
+ *   km          [num_slots, Hkv, D] storage dtype, or NULL   smooth-K mean PER SEQUENCE, fixed while the sequence lives
+ *   seqlens     int32 [num_slots], device                    valid keys per sequence
+ * Key j of the sequence in slot s lives in page block_table[s, j / page_size] at row j % page_size.  A page never splits a
+ * 64-key quantiser block or a 64-key tile of the decode kernel, so both calls do the arithmetic of their contiguous twins in
+ * the same order: the same appends give the same codes, scales and V, and the same decode gives the same O and LSE bit for bit
+ * (for the same num_splits).
+ *   slots : int32 [B] on the device or NULL - row b of the call (of k_new / v_new / new_lens, of q / o / lse) addresses slot
+ *           slots[b]; NULL: slot b.  B <= num_slots.  The slots of one append must be distinct (unchecked).
+ *   The host cannot check what is on the device: neither kernel ever forms an address from a slot outside [0, num_slots) or a
+ *   page outside [0, num_pages).  lbfa_decode_paged CLAMPS the id (a corrupt table gives a wrong answer, not a fault),
+ *   lbfa_kvcache_paged_append SKIPS the row / the 64-key block.  This defence is wave-uniform scalar work.
+ *
+ * lbfa_kvcache_paged_append: the contract of lbfa_kvcache_append.  new_lens is indexed by row of the call; seqlens, k_tail, km
+ * and block_table by slot.  The open block is re-quantised from k_tail plus the new rows: codes and scales are bit-identical
+ * to the dense quantiser on the concatenated K.  seqlens is read on the device and not advanced.  Rows beyond
+ * max_pages_per_seq * page_size are dropped.  The pages of the rows [seqlens[s], seqlens[s] + new_lens[b]) must be in the
+ * table before the call.  One workgroup owns both ends of the appended range.
+ *
+ * lbfa_decode_paged: the contract of lbfa_decode - M = Sq * (Hq / Hkv) <= 64, bottom-right causal alignment, num_splits, the
+ * same LSE definition, lbfa_decode_num_splits / lbfa_decode_workspace_bytes (called with B, not num_slots) and the same second
+ * kernel over the partials; max_seqlen_k in [1, max_pages_per_seq * page_size].  64-bit offsets everywhere: the pool may
+ * exceed 4 GiB.  Every host-visible argument is checked before the first launch (LBFA_EINVAL).
+ */
+int lbfa_kvcache_paged_append(const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
+                              int8_t* k_codes, float* k_scale, void* v_cache, void* k_tail, const int32_t* seqlens,
+                              const int32_t* block_table, const int32_t* slots, int B, int Hkv, int T, int D, int num_slots,
+                              int num_pages, int page_size, int max_pages_per_seq, const int64_t strides_k[3],
+                              const int64_t strides_v[3], int k_qmax, void* stream);
+int lbfa_decode_paged(const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const void* v_cache, const void* km,
+                      const int32_t* seqlens, const int32_t* block_table, const int32_t* slots, void* o, float* lse,
+                      void* workspace, size_t workspace_bytes, int B, int Hq, int Hkv, int Sq, int D, int num_slots, int num_pages,
+                      int page_size, int max_pages_per_seq, int max_seqlen_k, int num_splits, const int64_t strides_q[3],
+                      const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,8 @@ from .core import (  # noqa: F401
 from .kvcache import (  # noqa: F401
     # int8 KV cache + split-KV decode attention (no counterpart that works in the reference: SURVEY.md row 8)
     LowbitKVCache,
+    LowbitPagedKVCache,
+    PageAllocator,
     lowbit_fa_decode,
     sageattn_decode,
 )

@@ -82,6 +82,10 @@ SIGNATURES = {
     "lbfa_decode_workspace_bytes": (_sz, [_ci] * 7),
     "lbfa_decode": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci,
                           ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _cd, _ci, _ci, _vp]),
+    "lbfa_kvcache_paged_append": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci,
+                                        ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _ci, _vp]),
+    "lbfa_decode_paged": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _ci, _ci, _ci, _ci, _ci, _ci, _ci,
+                                _ci, _ci, _ci, _ci, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _cd, _ci, _ci, _vp]),
 }
 
 _lock = threading.Lock()

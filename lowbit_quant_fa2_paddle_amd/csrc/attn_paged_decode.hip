@@ -1,48 +1,50 @@
-// Split-KV decode attention over the int8 KV cache (kvcache.hip) for short queries, gfx950.
+// Split-KV decode attention over the PAGED int8 KV cache, gfx950: attn_decode_kernel (attn_decode.hip - layout of a tile, lane
+// roles and arithmetic are described there) with one table look-up per 64-key tile.
 //
-// One workgroup = ONE wave = one (batch, kv head, key slice) and all M = Sq * (Hq / Hkv) <= 64 query rows that share the kv head:
-// K codes and V are streamed once per GQA group.  The kernel is HBM-bound (3 D bytes per key), so it has none of the prefill
-// machinery: K fragments go from global memory straight to the registers the MFMA reads, V goes through a wave-private LDS
-// image only because the PV product needs it transposed, both one 64-key tile ahead of the arithmetic; parallelism comes from
-// the key slices (lbfa_decode_num_splits), a dozen waves per CU each with a tile in flight.
+// Pool: k_codes int8 / v fp16 [num_pages, Hkv, page_size, D], k_scale fp32 [num_pages, Hkv, page_size / 64]; key j of the sequence
+// in slot s lives in page block_table[s * max_pages + j / page_size], row j % page_size.  page_size is a multiple of 64, so a
+// tile - 64 D bytes of codes, 128 D bytes of V, one scale - is contiguous inside one page and the tile's arithmetic does not know
+// that it moved: same products in the same order per slice, the same partials for attn_decode_combine_kernel (whose workspace is
+// indexed by row of the call: nothing paged in it), results bit-identical to the contiguous cache for the same number of slices.
+// The look-up - slot of the row, page of the tile, both clamped into [0, num_slots) / [0, num_pages) because the host cannot
+// check device data - is wave-uniform scalar work.
 //
-// Arithmetic of a tile (the reference's kernel, attn_qk_int8_per_block.py:51-61, with P V accumulated in fp32):
-//   s = fp32(int32(q . k)) * q_scale * k_scale;  keys >= the row's limit -> -inf;  m' = max(m, rowmax);  p = exp2(s - m');
-//   l = l * exp2(m - m') + sum(p);  acc = acc * exp2(m - m') + fp16(p) V.
-// Q is quantised here, the Sq rows of one (batch, query head) as one block - what quant_per_block_kernel does for Sq <= 128 -
-// with the same fp32 operations (codes and scale bit-identical).
-//
-// Lane roles (i = lane & 15, g = lane >> 4), as in attn_fwd16.hip:
-//   S^T = K Q^T  (v_mfma_i32_16x16x64_i8)   A = K: key 16 kb + i, bytes [64 s + 16 g, +16);  B = Q: row 16 rb + i, same bytes;
-//                C: the lane holds, for ITS query row 16 rb + i, keys 16 kb + 4 g + {0..3}
-//   O^T += V^T P^T (v_mfma_f32_16x16x32_f16) B = P^T of k-step s: element j = key 32 s + 16 (j >> 2) + 4 g + (j & 3), the lane's
-//                own scores;  A = V^T in the same key order: two ds_read_b64_tr_b16 of the row-major V tile (rows
-//                32 s + 4 g + {0..3} and + 16);  C: for its query row, channels 16 cb + 4 g + {0..3}
-// V tile in LDS: [64 keys][2 D + 32 bytes]: the pad puts the 8 rows a 32-lane half reads at once on distinct banks.
-// Slices: tile range [split * tps, (split + 1) * tps) of the sequence's ceil(n / 64) tiles, tps = ceil(tiles / splits).  With
-// more than one slice each writes un-normalised fp32 acc and (m, l); attn_decode_combine_kernel adds them in one fixed order (no
-// atomics: bitwise reproducible for a given number of slices).
+// This is a COPY of attn_decode_kernel's text, not a shared body: with one __device__ body behind a PAGED flag the compiler moved
+// instructions of all twelve contiguous instances (an operand swap in the prologue's adds, other register assignments), and
+// that kernel has to stay the parent's instruction for instruction.  A change to the arithmetic of one belongs in the other too;
+// tests/test_gpu_paged_kvcache.py holds the two to torch.equal.
 #include "attn_common.h"
 
 namespace lbfa {
 
+hipError_t launch_attn_decode_combine(const DecodeParams& p, int dtype, int D, hipStream_t stream);  // attn_decode.hip
+
+namespace {
 typedef short s16x4v __attribute__((ext_vector_type(4)));
-constexpr float kLog2e = 1.44269504f;  // the literal of src/core.py:347; the natural-log LSE is a correctly rounded division by it
+constexpr float kLog2e = 1.44269504f;  // as attn_decode.hip
+}  // namespace
 
 template <int DT, int D, int MB>
-__global__ __launch_bounds__(64) void attn_decode_kernel(DecodeParams p) {
+__global__ __launch_bounds__(64) void attn_paged_decode_kernel(PagedDecodeParams p) {
   constexpr int KS = D / 64;        // k-steps of the score product
   constexpr int CB = D / 16;        // 16-channel blocks of O^T
   constexpr int VROW = 2 * D + 32;  // bytes per LDS row
   constexpr int VCH = D / 8;        // 16-byte chunks of a V tile per lane
+  typedef int64_t tile_t;           // what names a tile to the loads, see locate()
   __shared__ __attribute__((aligned(16))) unsigned char smem[64 * VROW];
   const int split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
   const int lane = threadIdx.x, i16 = lane & 15, g = lane >> 4;
-  const int n = min(max(p.seqlens[b], 0), p.max_k);
+  // b is the ROW of the call (q, o, lse, workspace); seqlens, km and the block table belong to its slot.  Slot and page ids are
+  // device data the host cannot check: both are clamped into range (wave-uniform scalar work), so a corrupt table gives a wrong
+  // answer, never an address outside the pool.
+  int sl = p.slots != nullptr ? p.slots[b] : b;
+  sl = __builtin_amdgcn_readfirstlane(min(max(sl, 0), p.num_slots - 1));
+  const int n = min(max(p.seqlens[sl], 0), p.max_k);
   const int ntiles = (n + 63) >> 6;
   const int tps = (ntiles + p.splits - 1) / p.splits;
   const int t0 = split * tps, t1 = min(t0 + tps, ntiles);
   const int64_t bh = (int64_t)b * p.Hkv + hk;
+  const int64_t sh = (int64_t)sl * p.Hkv + hk;  // (slot, kv head): km
 
   // ---- query rows of this lane: load, quantise, q . km ---------------------------------------------------------------
   int row[MB], hq[MB], sq[MB], lim[MB];
@@ -73,8 +75,8 @@ __global__ __launch_bounds__(64) void attn_decode_kernel(DecodeParams p) {
         }
         uint4 kmr[2] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
         if (p.km != nullptr) {
-          kmr[0] = *reinterpret_cast<const uint4*>(p.km + bh * D + 64 * s + 16 * g);
-          kmr[1] = *reinterpret_cast<const uint4*>(p.km + bh * D + 64 * s + 16 * g + 8);
+          kmr[0] = *reinterpret_cast<const uint4*>(p.km + sh * D + 64 * s + 16 * g);
+          kmr[1] = *reinterpret_cast<const uint4*>(p.km + sh * D + 64 * s + 16 * g + 8);
         }
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
@@ -136,21 +138,33 @@ __global__ __launch_bounds__(64) void attn_decode_kernel(DecodeParams p) {
     for (int cb = 0; cb < CB; ++cb) acc[rb][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
 
-  const int8_t* kbase = p.k_codes + bh * (int64_t)p.cap * D + (int64_t)i16 * D + 16 * g;
-  const unsigned short* vbase = p.v + bh * (int64_t)p.cap * D;
-  const float* ksc = p.k_scale + bh * (p.cap >> 6);
+  // Where tile t of the sequence lives: tile `gt` of the POOL seen as [num_pages, Hkv, page_size / 64] tiles of 64 keys - codes, V
+  // and scale of a tile are all found from that one 64-bit number, and nothing else in a tile's computation knows where the tile
+  // lives.  fetch() is the table load, locate() the arithmetic on its result: the loop fetches the page id of the tile AFTER the
+  // look-ahead tile, so that no K / V load waits behind a fresh table load.  All of it depends on blockIdx and the loop counter
+  // only: scalar registers, one scalar divide per tile (page_size is any multiple of 64, not only a power of two).
+  const int8_t* kbase = p.k_codes + (int64_t)i16 * D + 16 * g;
+  const unsigned short* vbase = p.v;
+  const float* ksc = p.k_scale;
+  const int tpp = p.page_size >> 6;  // tiles per page
+  const int* tbl = p.block_table + (int64_t)sl * p.max_pages;
+  auto fetch = [&](int t) __attribute__((always_inline)) -> int { return tbl[t / tpp]; };
+  auto locate = [&](int t, int pg) __attribute__((always_inline)) -> tile_t {
+    pg = __builtin_amdgcn_readfirstlane(min(max(pg, 0), p.num_pages - 1));
+    return ((int64_t)pg * p.Hkv + hk) * tpp + t % tpp;
+  };
   typedef __attribute__((address_space(3))) unsigned char lds_byte;
   typedef __attribute__((address_space(3))) s16x4v lds_s16x4;
   lds_byte* const vt_lane = (lds_byte*)smem + (4 * g + (i16 >> 2)) * VROW + (i16 & 3) * 8;
 
-  auto load_k = [&](int t, i32x4 (&kf)[4][KS]) __attribute__((always_inline)) {
+  auto load_k = [&](tile_t t, i32x4 (&kf)[4][KS]) __attribute__((always_inline)) {
     const int8_t* kt = kbase + (int64_t)t * 64 * D;
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
       for (int s = 0; s < KS; ++s) kf[kb][s] = *reinterpret_cast<const i32x4*>(kt + kb * 16 * D + 64 * s);
   };
-  auto load_v = [&](int t, uint4 (&vr)[VCH]) __attribute__((always_inline)) {
+  auto load_v = [&](tile_t t, uint4 (&vr)[VCH]) __attribute__((always_inline)) {
     const unsigned short* vt = vbase + (int64_t)t * 64 * D;
 #pragma unroll
     for (int u = 0; u < VCH; ++u) vr[u] = *reinterpret_cast<const uint4*>(vt + (u * 64 + lane) * 8);  // the tile is contiguous
@@ -164,8 +178,8 @@ __global__ __launch_bounds__(64) void attn_decode_kernel(DecodeParams p) {
       *reinterpret_cast<uint4*>(smem + r * VROW + ch * 16) = val;
     }
   };
-  auto compute = [&](int t, const i32x4 (&kf)[4][KS]) __attribute__((always_inline)) {
-    const float kscale = ksc[t];
+  auto compute = [&](int t, tile_t gt, const i32x4 (&kf)[4][KS]) __attribute__((always_inline)) {
+    const float kscale = ksc[gt];
 #pragma unroll
     for (int rb = 0; rb < MB; ++rb) {
       float sc[4][4];
@@ -226,37 +240,46 @@ __global__ __launch_bounds__(64) void attn_decode_kernel(DecodeParams p) {
     if (t0 < t1) {
       i32x4 ka[4][KS], kb_[4][KS];
       uint4 vr[VCH];
-      load_k(t0, ka);
-      load_v(t0, vr);
+      tile_t ga = locate(t0, fetch(t0)), gb;
+      int pn = fetch(min(t0 + 1, t1 - 1));  // page id of the NEXT look-ahead tile, on its way one step early
+      load_k(ga, ka);
+      load_v(ga, vr);
       store_v(t0, vr);
       __syncthreads();
       for (int t = t0; t < t1; t += 2) {
         const int ta = min(t + 1, t1 - 1);
-        load_k(ta, kb_);
-        load_v(ta, vr);
-        compute(t, ka);
+        gb = locate(ta, pn);
+        pn = fetch(min(t + 2, t1 - 1));
+        load_k(gb, kb_);
+        load_v(gb, vr);
+        compute(t, ga, ka);
         __syncthreads();
         if (t + 1 >= t1) break;
         store_v(ta, vr);
         __syncthreads();
         const int tb = min(t + 2, t1 - 1);
-        load_k(tb, ka);
-        load_v(tb, vr);
-        compute(t + 1, kb_);
+        ga = locate(tb, pn);
+        pn = fetch(min(t + 3, t1 - 1));
+        load_k(ga, ka);
+        load_v(ga, vr);
+        compute(t + 1, gb, kb_);
         __syncthreads();
         store_v(tb, vr);
         __syncthreads();
       }
     }
   } else {
+    int pn = t0 < t1 ? fetch(t0) : 0;
     for (int t = t0; t < t1; ++t) {
       i32x4 ka[4][KS];
       uint4 vr[VCH];
-      load_k(t, ka);
-      load_v(t, vr);
+      const tile_t ga = locate(t, pn);
+      pn = fetch(min(t + 1, t1 - 1));
+      load_k(ga, ka);
+      load_v(ga, vr);
       store_v(t, vr);
       __syncthreads();
-      compute(t, ka);
+      compute(t, ga, ka);
       __syncthreads();
     }
   }
@@ -294,87 +317,11 @@ __global__ __launch_bounds__(64) void attn_decode_kernel(DecodeParams p) {
   }
 }
 
-// Adds the slices of one query row: m = max m_s, l = sum l_s 2^(m_s - m), O = sum acc_s 2^(m_s - m) / l, in ONE fixed order - the
-// 256 threads are 256 / D groups of one thread per channel, group g adds its contiguous run of ceil(splits / groups) slices in
-// slice order (eight independent loads in flight: a dependent chain over 128 slices cost three times the decode kernel itself),
-// then the groups are added in group order.  A slice that saw no key (m_s = -inf) is skipped - its acc may never have been
-// written.
-template <int DT, int D>
-__global__ __launch_bounds__(256) void attn_decode_combine_kernel(DecodeParams p) {
-  constexpr int NG = 256 / D, NB = 8;
-  __shared__ float red[256];
-  __shared__ float part_a[NG][D];
-  __shared__ float part_l[NG];
-  const int r = blockIdx.x, hk = blockIdx.y, b = blockIdx.z, t = threadIdx.x, d = t % D, grp = t / D;
-  const int64_t bh = (int64_t)b * p.Hkv + hk;
-  const float* ml = p.ws_ml + (bh * p.splits * p.M + r) * 4;
-  const float* ap = p.ws_acc + (bh * p.splits * p.M + r) * D + d;
-  const int64_t sstep = (int64_t)p.M;
-  const float ninf = -__builtin_inff();
-  float m = ninf;
-  for (int s = t; s < p.splits; s += 256) m = fmaxf(m, ml[s * sstep * 4]);
-  red[t] = m;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {  // a maximum: any order gives the same bits
-    if (t < o) red[t] = fmaxf(red[t], red[t + o]);
-    __syncthreads();
-  }
-  m = red[0];
-  const int chunk = (p.splits + NG - 1) / NG, s_lo = grp * chunk, s_hi = min(s_lo + chunk, p.splits);
-  float l = 0.f, a = 0.f;
-  if (m != ninf)
-    for (int s0 = s_lo; s0 < s_hi; s0 += NB) {
-      float ms[NB], ls[NB], as[NB];
-#pragma unroll
-      for (int j = 0; j < NB; ++j) {  // the index is clamped, not the load skipped: all NB loads go out together
-        const int64_t sj = min(s0 + j, s_hi - 1) * sstep;
-        ms[j] = ml[sj * 4];
-        ls[j] = ml[sj * 4 + 1];
-        as[j] = ap[sj * D];
-      }
-#pragma unroll
-      for (int j = 0; j < NB; ++j)
-        if (s0 + j < s_hi && ms[j] != ninf) {
-          const float w = __builtin_amdgcn_exp2f(ms[j] - m);
-          l = l + ls[j] * w;
-          a = a + as[j] * w;
-        }
-    }
-  part_a[grp][d] = a;
-  if (d == 0) part_l[grp] = l;
-  __syncthreads();
-  if (grp != 0) return;
-  l = part_l[0];
-  a = part_a[0][d];
-#pragma unroll
-  for (int g2 = 1; g2 < NG; ++g2) {
-    l = l + part_l[g2];
-    a = a + part_a[g2][d];
-  }
-  const int hl = r / p.Sq, sq = r - hl * p.Sq, hq = hk * p.group + hl;
-  const float inv = l > 0.f ? 1.0f / l : 0.f;
-  reinterpret_cast<unsigned short*>(p.o)[(int64_t)b * p.ob + (int64_t)hq * p.oh + (int64_t)sq * p.os + d] = store_cvt<DT>(a * inv);
-  if (p.lse != nullptr && d == 0) {
-    const float lse2 = l > 0.f ? __builtin_amdgcn_logf(l) + m : ninf;
-    p.lse[((int64_t)b * p.Hq + hq) * p.Sq + sq] = lse2 / kLog2e + ml[2] * p.corr_scale;
-  }
-}
-
-// the second launch of a call with more than one slice; the paged kernel (attn_paged_decode.hip) leaves the same partials
-hipError_t launch_attn_decode_combine(const DecodeParams& p, int dtype, int D, hipStream_t stream) {
-  dim3 g2(p.M, p.Hkv, p.B);
-#define LBFA_CMB(DT, DD) hipLaunchKernelGGL((attn_decode_combine_kernel<DT, DD>), g2, dim3(256), 0, stream, p)
-  if (dtype == LBFA_F16) { if (D == 64) LBFA_CMB(LBFA_F16, 64); else LBFA_CMB(LBFA_F16, 128); }
-  else { if (D == 64) LBFA_CMB(LBFA_BF16, 64); else LBFA_CMB(LBFA_BF16, 128); }
-#undef LBFA_CMB
-  return hipGetLastError();
-}
-
 // ---- host-side launcher (called from lbfa_api.hip) -----------------------------------------------------------------------
-hipError_t launch_attn_decode(const DecodeParams& p, int dtype, int D, hipStream_t stream) {
+hipError_t launch_attn_paged_decode(const PagedDecodeParams& p, int dtype, int D, hipStream_t stream) {
   dim3 grid(p.splits, p.Hkv, p.B);
   const int mb = (p.M + 15) / 16;
-#define LBFA_DEC(DT, DD, MB) hipLaunchKernelGGL((attn_decode_kernel<DT, DD, MB>), grid, dim3(64), 0, stream, p)
+#define LBFA_DEC(DT, DD, MB) hipLaunchKernelGGL((attn_paged_decode_kernel<DT, DD, MB>), grid, dim3(64), 0, stream, p)
 #define LBFA_DEC1(DT, DD)                 \
   do {                                    \
     if (mb <= 1) LBFA_DEC(DT, DD, 1);     \
@@ -387,7 +334,7 @@ hipError_t launch_attn_decode(const DecodeParams& p, int dtype, int D, hipStream
 #undef LBFA_DEC
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || p.splits == 1) return e;
-  return launch_attn_decode_combine(p, dtype, D, stream);
+  return launch_attn_decode_combine(p, dtype, D, stream);  // the partials are indexed by row of the call: nothing paged in them
 }
 
 }  // namespace lbfa

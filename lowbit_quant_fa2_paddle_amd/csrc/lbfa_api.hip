@@ -27,6 +27,9 @@ hipError_t launch_attn_bwd(const BwdParams& p, int dtype, bool quant, bool causa
 hipError_t launch_kvcache_append(const AppendParams& p, int dtype, int D, hipStream_t stream);
 hipError_t launch_kvcache_mean(const RaggedMeanParams& p, int dtype, int B, int D, hipStream_t stream);
 hipError_t launch_attn_decode(const DecodeParams& p, int dtype, int D, hipStream_t stream);
+// defined in kvcache_paged.hip / attn_paged_decode.hip
+hipError_t launch_kvcache_paged_append(const PagedAppendParams& p, int dtype, int D, hipStream_t stream);
+hipError_t launch_attn_paged_decode(const PagedDecodeParams& p, int dtype, int D, hipStream_t stream);
 }  // namespace lbfa
 
 namespace {
@@ -1055,6 +1058,117 @@ int lbfa_decode(const void* q, int dtype, const int8_t* k_codes, const float* k_
   }
   g_err[0] = 0;
   return check_hip(lbfa::launch_attn_decode(p, dtype, D, (hipStream_t)stream), "lbfa_decode launch");
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// the same two calls over a pool of pages behind a block table (kvcache_paged.hip, attn_paged_decode.hip)
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+// 0, or the refusal; on success *cap = max_pages_per_seq * page_size, the most keys a sequence can hold
+int check_pool(const char* who, int B, int num_slots, int num_pages, int page_size, int max_pages_per_seq, int* cap) {
+  if (page_size <= 0 || page_size % LBFA_BLKK != 0)
+    return fail(LBFA_EINVAL, "%s: page_size must be a positive multiple of 64, got %d", who, page_size);
+  if (num_pages < 1 || num_slots < 1 || max_pages_per_seq < 1)
+    return fail(LBFA_EINVAL, "%s: num_pages, num_slots and max_pages_per_seq must be at least 1, got %d, %d and %d", who, num_pages,
+                num_slots, max_pages_per_seq);
+  if ((int64_t)max_pages_per_seq * page_size > 0x7fffffffLL)
+    return fail(LBFA_EINVAL, "%s: max_pages_per_seq * page_size must stay below 2^31 keys", who);
+  if (B > num_slots) return fail(LBFA_EINVAL, "%s: B (%d) exceeds num_slots (%d)", who, B, num_slots);
+  *cap = max_pages_per_seq * page_size;
+  return 0;
+}
+}  // namespace
+
+int lbfa_kvcache_paged_append(const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
+                              int8_t* k_codes, float* k_scale, void* v_cache, void* k_tail, const int32_t* seqlens,
+                              const int32_t* block_table, const int32_t* slots, int B, int Hkv, int T, int D, int num_slots,
+                              int num_pages, int page_size, int max_pages_per_seq, const int64_t strides_k[3],
+                              const int64_t strides_v[3], int k_qmax, void* stream) {
+  const char* who = "lbfa_kvcache_paged_append";
+  const Operand tk = dense(k_new, strides_k), tv = dense(v_new, strides_v);
+  if (!tk.p || !tv.p || !k_codes || !k_scale || !v_cache || !k_tail || !seqlens || !block_table) return fail(LBFA_EINVAL, "%s: null pointer", who);
+  if (B <= 0 || Hkv <= 0 || T <= 0) return fail(LBFA_EINVAL, "%s: empty tensor", who);
+  if (int st = check_head_dim(D, false)) return st;
+  int cap = 0;
+  if (int st = check_pool(who, B, num_slots, num_pages, page_size, max_pages_per_seq, &cap)) return st;
+  if (int st = check_dtype(dtype)) return st;
+  if (int st = check_qmax(who, "k_qmax", k_qmax)) return st;
+  if (int st = check_input16(who, "k_new", tk)) return st;
+  if (int st = check_input16(who, "v_new", tv)) return st;
+  if (!aligned(k_codes, 16) || !aligned(v_cache, 16) || !aligned(k_tail, 16) || !aligned(km, 16) || !aligned(k_scale, 4) ||
+      !aligned(seqlens, 4) || !aligned(new_lens, 4) || !aligned(block_table, 4) || !aligned(slots, 4))
+    return fail(LBFA_EINVAL, "%s: cache tensors and km must be 16-byte aligned, k_scale / seqlens / new_lens / block_table / slots 4-byte aligned", who);
+  if (B > 65535 || Hkv > 65535) return fail(LBFA_EINVAL, "%s: grid too large", who);
+  lbfa::PagedAppendParams p{};
+  p.k_new = (const unsigned short*)k_new; p.v_new = (const unsigned short*)v_new;
+  p.new_lens = new_lens; p.km = (const unsigned short*)km;
+  p.k_codes = k_codes; p.k_scale = k_scale; p.v = (unsigned short*)v_cache; p.k_tail = (unsigned short*)k_tail;
+  p.seqlens = seqlens;
+  p.kb = tk.st[0]; p.kh = tk.st[1]; p.ks = tk.st[2];
+  p.vb = tv.st[0]; p.vh = tv.st[1]; p.vs = tv.st[2];
+  p.B = B; p.Hkv = Hkv; p.T = T; p.cap = cap;
+  p.qmax = (float)k_qmax;
+  p.block_table = block_table; p.slots = slots;
+  p.num_slots = num_slots; p.num_pages = num_pages; p.page_size = page_size; p.max_pages = max_pages_per_seq;
+  g_err[0] = 0;
+  return check_hip(lbfa::launch_kvcache_paged_append(p, dtype, D, (hipStream_t)stream), "lbfa_kvcache_paged_append launch");
+}
+
+int lbfa_decode_paged(const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const void* v_cache, const void* km,
+                      const int32_t* seqlens, const int32_t* block_table, const int32_t* slots, void* o, float* lse,
+                      void* workspace, size_t workspace_bytes, int B, int Hq, int Hkv, int Sq, int D, int num_slots, int num_pages,
+                      int page_size, int max_pages_per_seq, int max_seqlen_k, int num_splits, const int64_t strides_q[3],
+                      const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream) {
+  const char* who = "lbfa_decode_paged";
+  const Operand tq = dense(q, strides_q), to = dense(o, strides_o);
+  if (!tq.p || !to.p || !k_codes || !k_scale || !v_cache || !seqlens || !block_table) return fail(LBFA_EINVAL, "%s: null pointer", who);
+  if (B <= 0 || Hq <= 0 || Hkv <= 0 || Sq <= 0) return fail(LBFA_EINVAL, "%s: empty tensor", who);
+  if (int st = check_head_dim(D, false)) return st;
+  if (int st = check_gqa(Hq, Hkv)) return st;
+  const int64_t M = (int64_t)Sq * (Hq / Hkv);
+  if (M > kDecodeMaxRows)
+    return fail(LBFA_EINVAL, "%s: Sq * (Hq / Hkv) = %lld query rows per kv head, the limit is %d (longer queries belong on the dense operator)",
+                who, (long long)M, kDecodeMaxRows);
+  int cap = 0;
+  if (int st = check_pool(who, B, num_slots, num_pages, page_size, max_pages_per_seq, &cap)) return st;
+  if (max_seqlen_k < 1 || max_seqlen_k > cap)
+    return fail(LBFA_EINVAL, "%s: max_seqlen_k must be in [1, max_pages_per_seq * page_size], got %d (limit %d)", who, max_seqlen_k, cap);
+  if (num_splits < 0 || num_splits > 65535) return fail(LBFA_EINVAL, "%s: num_splits must be in [0, 65535] (0: chosen by lbfa_decode_num_splits), got %d", who, num_splits);
+  if (int st = check_dtype(dtype)) return st;
+  if (int st = check_qmax(who, "q_qmax", q_qmax)) return st;
+  if (!(sm_scale > 0.0)) return fail(LBFA_EINVAL, "%s: sm_scale must be positive", who);
+  if (int st = check_input16(who, "q", tq)) return st;
+  if (!aligned(to, 8, 4)) return fail(LBFA_EINVAL, "%s: o must be 8-byte aligned with strides that are multiples of 4 elements", who);
+  if (!aligned(k_codes, 16) || !aligned(v_cache, 16) || !aligned(km, 16) || !aligned(k_scale, 4) || !aligned(seqlens, 4) ||
+      !aligned(block_table, 4) || !aligned(slots, 4) || !aligned(lse, 4))
+    return fail(LBFA_EINVAL, "%s: cache tensors and km must be 16-byte aligned, k_scale / seqlens / block_table / slots / lse 4-byte aligned", who);
+  const int splits = num_splits ? num_splits : lbfa_decode_num_splits(B, Hkv, max_seqlen_k);
+  const size_t need = lbfa_decode_workspace_bytes(B, Hq, Hkv, Sq, D, max_seqlen_k, splits);
+  if (need) {
+    if (int st = check_workspace(who, workspace, workspace_bytes, need)) return st;
+    if (!workspace) return fail(LBFA_EINVAL, "%s: null pointer", who);
+  }
+  if (B > 65535 || Hkv > 65535) return fail(LBFA_EINVAL, "%s: grid too large", who);
+  lbfa::PagedDecodeParams p{};
+  p.q = (const unsigned short*)q; p.k_codes = k_codes; p.k_scale = k_scale; p.v = (const unsigned short*)v_cache;
+  p.km = lse ? (const unsigned short*)km : nullptr;  // km only enters the LSE correction
+  p.seqlens = seqlens; p.o = o; p.lse = lse;
+  p.qb = tq.st[0]; p.qh = tq.st[1]; p.qs = tq.st[2];
+  p.ob = to.st[0]; p.oh = to.st[1]; p.os = to.st[2];
+  p.B = B; p.Hq = Hq; p.Hkv = Hkv; p.Sq = Sq; p.group = Hq / Hkv; p.M = (int)M;
+  p.cap = cap; p.max_k = max_seqlen_k; p.splits = splits; p.causal = is_causal ? 1 : 0;
+  p.q_sm_scale = (float)(sm_scale * 1.44269504);  // ONE rounding of the double product, as lbfa_decode
+  p.q_qmax = (float)q_qmax;
+  p.corr_scale = (float)sm_scale;
+  if (splits > 1) {
+    const size_t rows = (size_t)B * Hkv * splits * (size_t)M;
+    p.ws_acc = (float*)workspace;
+    p.ws_ml = (float*)((char*)workspace + align256(rows * D * sizeof(float)));
+  }
+  p.block_table = block_table; p.slots = slots;
+  p.num_slots = num_slots; p.num_pages = num_pages; p.page_size = page_size; p.max_pages = max_pages_per_seq;
+  g_err[0] = 0;
+  return check_hip(lbfa::launch_attn_paged_decode(p, dtype, D, (hipStream_t)stream), "lbfa_decode_paged launch");
 }
 
 }  // extern "C"

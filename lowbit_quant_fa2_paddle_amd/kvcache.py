@@ -5,12 +5,16 @@ prefill appended to an empty cache holds exactly the codes `lowbit_fa_qk_int8_pv
 is appended to in place (`lbfa_kvcache_append`).  `lowbit_fa_decode` attends a few new queries (Sq * Hq / Hkv <= 64 rows per kv
 head) to the cache with one split-KV kernel (`lbfa_decode`): K and V are read once per GQA group, nothing is re-quantised.
 
-Not here: paged / block-table caches, an fp8 V cache (its per-channel scale needs the whole sequence), nibble-packed int4
+`LowbitPagedKVCache` is the same cache as a pool of fixed-size pages behind one block table per sequence slot
+(`lbfa_kvcache_paged_append`, `lbfa_decode_paged`): sequences of any length share the pool, a finished one gives its pages back,
+and every sequence has a smooth-K mean of its own.  State and decode results equal the contiguous cache's bit for bit.
+
+Not here: prefix sharing / copy-on-write between sequences, an fp8 V cache (its per-channel scale needs the whole sequence), nibble-packed int4
 (the +-7 codes take a byte each), a backward through the cache, Paddle tensors.
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Iterable, Optional, Sequence
 
 from . import _lib
 from . import quant_per_block as _qpb
@@ -128,19 +132,240 @@ class LowbitKVCache:
         return k[..., :self.head_dim]
 
 
-def lowbit_fa_decode(q, cache: LowbitKVCache, tensor_layout: str = "HND", is_causal: bool = False,
-                     sm_scale: Optional[float] = None, return_lse: bool = False, num_splits: int = 0, q_bits: int = 8):
+class PageAllocator:
+    """Host side of a paged cache, pure Python (no device, no tensors): a free list of page ids, the pages each sequence slot
+    holds in order, and per slot an upper bound of the rows offered so far.  Pages are handed out from the front of the free
+    list (initially `page_order`, a permutation of range(num_pages), or range(num_pages)) and come back at its end."""
+
+    def __init__(self, num_pages: int, page_size: int, max_seqs: int, max_pages_per_seq: int,
+                 page_order: Optional[Iterable[int]] = None):
+        if num_pages < 1 or max_seqs < 1 or max_pages_per_seq < 1:
+            raise ValueError("num_pages, max_seqs and max_pages_per_seq must be at least 1")
+        if page_size < 1 or page_size % _lib.BLKK:
+            raise ValueError(f"page_size must be a positive multiple of {_lib.BLKK}, got {page_size}")
+        order = list(range(num_pages)) if page_order is None else [int(x) for x in page_order]
+        if sorted(order) != list(range(num_pages)):
+            raise ValueError("page_order must be a permutation of range(num_pages)")
+        self.num_pages, self.page_size = int(num_pages), int(page_size)
+        self.max_seqs, self.max_pages_per_seq = int(max_seqs), int(max_pages_per_seq)
+        self.free_pages = order
+        self.pages = [[] for _ in range(self.max_seqs)]   # pages of each slot, in sequence order
+        self.bound = [0] * self.max_seqs                  # rows offered to each slot: an upper bound of its length
+
+    @property
+    def capacity(self) -> int:
+        return self.max_pages_per_seq * self.page_size
+
+    @property
+    def num_free_pages(self) -> int:
+        return len(self.free_pages)
+
+    def reserve(self, slots: Sequence[int], T: int):
+        """Make room for T more rows in each of `slots`: -> [(slot, index in the slot's table, page)] of the new table entries.
+        All or nothing: ValueError (a slot would pass the capacity) or RuntimeError (out of pages) leave everything as it was."""
+        need = []
+        for s in slots:
+            if self.bound[s] + T > self.capacity:
+                raise ValueError(f"appending {T} tokens to at most {self.bound[s]} in slot {s} would pass the capacity "
+                                 f"{self.capacity} (max_pages_per_seq * page_size)")
+            need.append(-(-(self.bound[s] + T) // self.page_size) - len(self.pages[s]))
+        if sum(need) > len(self.free_pages):
+            raise RuntimeError(f"out of pages: the append needs {sum(need)} more, {len(self.free_pages)} are free")
+        changed = []
+        for s, k in zip(slots, need):
+            for _ in range(k):
+                page = self.free_pages.pop(0)
+                changed.append((s, len(self.pages[s]), page))
+                self.pages[s].append(page)
+            self.bound[s] += T
+        return changed
+
+    def release(self, slot: int):
+        """Give the pages of `slot` back (in the order it held them) and make it fresh: -> those pages"""
+        pages, self.pages[slot], self.bound[slot] = self.pages[slot], [], 0
+        self.free_pages.extend(pages)
+        return pages
+
+
+def _slot_list(slots, n: int, max_seqs: int):
+    """the slots of a call with n rows: distinct ints in [0, max_seqs); None: all slots in order"""
+    if slots is None:
+        if n != max_seqs:
+            raise ValueError(f"slots=None addresses all {max_seqs} slots, got {n} rows")
+        return list(range(max_seqs))
+    slots = [int(x) for x in slots]
+    if len(slots) != n:
+        raise ValueError(f"expected one slot per row ({n}), got {len(slots)}")
+    if len(set(slots)) != len(slots):
+        raise ValueError(f"slots must be distinct, got {slots}")
+    if any(x < 0 or x >= max_seqs for x in slots):
+        raise ValueError(f"slots must be in [0, {max_seqs}), got {slots}")
+    return slots
+
+
+class LowbitPagedKVCache:
+    """The int8 KV cache as a pool of `num_pages` pages of `page_size` keys (a multiple of 64) shared by up to `max_seqs`
+    sequences, each in a slot with a block table of up to `max_pages_per_seq` pages.
+
+    State (public, all on `device`; the layout `lbfa_kvcache_paged_append` / `lbfa_decode_paged` take): k_codes int8
+    [num_pages, Hkv, page_size, Dp], k_scale fp32 [num_pages, Hkv, page_size / 64], v fp16 [num_pages, Hkv, page_size, Dp],
+    block_table int32 [max_seqs, max_pages_per_seq], k_tail [max_seqs, Hkv, 64, Dp], km [max_seqs, Hkv, Dp] or None, seqlens int32
+    [max_seqs].  `allocator` (a `PageAllocator`) is the host side.  `km` is PER SEQUENCE: a slot that holds nothing is fresh, and
+    takes its mean from its first append.  As in `LowbitKVCache` no host read of device lengths happens anywhere: pages are
+    allocated for the upper bound of each length."""
+
+    def __init__(self, num_pages: int, page_size: int, num_kv_heads: int, head_dim: int, max_seqs: int, max_pages_per_seq: int,
+                 dtype, device, k_bits: int = 8, smooth_k: bool = True, page_order: Optional[Iterable[int]] = None):
+        import torch
+        if k_bits not in (8, 4):
+            raise ValueError(f"k_bits must be 8 or 4, got {k_bits}")
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError("dtype must be torch.float16 or torch.bfloat16")
+        if num_kv_heads <= 0:
+            raise ValueError("num_kv_heads must be positive")
+        self.allocator = PageAllocator(num_pages, page_size, max_seqs, max_pages_per_seq, page_order)
+        self.num_pages, self.page_size = self.allocator.num_pages, self.allocator.page_size
+        self.max_seqs, self.max_pages_per_seq = self.allocator.max_seqs, self.allocator.max_pages_per_seq
+        self.num_kv_heads, self.head_dim = int(num_kv_heads), int(head_dim)
+        self.padded_head_dim = _padded_head_dim(self.head_dim)
+        self.dtype, self.device = dtype, torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("LowbitPagedKVCache lives on an AMD GPU (gfx950) only; there is no CPU fallback.")
+        self.k_qmax = 127 if k_bits == 8 else 7
+        self.smooth_k = bool(smooth_k)
+        N, S, H, P, D = self.num_pages, self.max_seqs, self.num_kv_heads, self.page_size, self.padded_head_dim
+        self.k_codes = torch.zeros((N, H, P, D), dtype=torch.int8, device=self.device)
+        self.k_scale = torch.zeros((N, H, P // _lib.BLKK), dtype=torch.float32, device=self.device)
+        self.v = torch.zeros((N, H, P, D), dtype=torch.float16, device=self.device)
+        self.block_table = torch.zeros((S, self.max_pages_per_seq), dtype=torch.int32, device=self.device)
+        self.k_tail = torch.zeros((S, H, _lib.BLKK, D), dtype=dtype, device=self.device)
+        self.km = torch.zeros((S, H, D), dtype=dtype, device=self.device) if self.smooth_k else None
+        self.seqlens = torch.zeros((S,), dtype=torch.int32, device=self.device)
+
+    @property
+    def num_free_pages(self) -> int:
+        return self.allocator.num_free_pages
+
+    def append(self, k, v, slots=None, tensor_layout: str = "HND", new_lens=None):
+        """Append k, v [n, Hkv, T, D] ("HND") or [n, T, Hkv, D] ("NHD") to the sequences in `slots` (n distinct ints; None: all
+        max_seqs slots in order); row b takes the first new_lens[b] rows (an int32 device tensor [n], None: all T).  Pages for
+        T more rows per slot are taken before the launch: RuntimeError ("out of pages") or ValueError (a slot would pass
+        max_pages_per_seq * page_size) leave the cache as it was.  Returns self."""
+        slots_given = slots is not None
+        slots = _slot_list(slots, int(k.shape[0]), self.max_seqs)
+        ops = ops_for(k)
+        torch = ops.torch
+        if tensor_layout not in ("HND", "NHD"):
+            raise ValueError(f"Unknown tensor layout: {tensor_layout}")
+        if k.dtype != self.dtype or v.dtype != self.dtype:
+            raise ValueError("k and v must have the dtype of the cache")
+        if k.device != self.device or v.device != self.device:
+            raise ValueError("k and v must be on the device of the cache")
+        if tuple(k.shape) != tuple(v.shape) or k.dim() != 4:
+            raise ValueError("k and v must be 4-D tensors of the same shape")
+        pad = self.padded_head_dim - self.head_dim
+        if k.shape[-1] != self.head_dim:
+            raise ValueError(f"head_dim {k.shape[-1]} does not match the cache ({self.head_dim})")
+        if pad:  # only the new tokens are padded
+            k, v = ops.pad_last(k, pad), ops.pad_last(v, pad)
+        if k.stride(-1) != 1:
+            k = k.contiguous()
+        if v.stride(-1) != 1:
+            v = v.contiguous()
+        (n, H, T), k3 = _qpb._bhs(ops.shape(k), ops.strides(k), tensor_layout)
+        (_, _, _), v3 = _qpb._bhs(ops.shape(v), ops.strides(v), tensor_layout)
+        if H != self.num_kv_heads:
+            raise ValueError(f"expected {self.num_kv_heads} kv heads, got {H}")
+        if T == 0:
+            return self
+        if new_lens is not None:
+            new_lens = new_lens.to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(new_lens.shape) != (n,):
+                raise ValueError("new_lens must have one entry per row")
+        fresh = [i for i, s in enumerate(slots) if self.allocator.bound[s] == 0]  # rows whose sequence starts here
+        changed = self.allocator.reserve(slots, T)  # raises with nothing changed
+        lib = _lib.load()
+        D, code = self.padded_head_dim, ops.dtype_code(k)
+        with ops.device_guard(k):
+            stream = ops.stream(k)
+            if changed:  # only the new table entries travel
+                flat = torch.tensor([s * self.max_pages_per_seq + i for s, i, _ in changed], dtype=torch.int64, device=self.device)
+                self.block_table.view(-1).index_copy_(0, flat, torch.tensor([pg for _, _, pg in changed], dtype=torch.int32,
+                                                                           device=self.device))
+            slot_t = torch.tensor(slots, dtype=torch.int32, device=self.device) if slots_given else None
+            if self.smooth_k and fresh:
+                km_new = torch.empty((n, H, D), dtype=self.dtype, device=self.device)
+                if new_lens is None:  # the mean of the dense operators: the codes of a prefill are theirs
+                    ws_bytes = lib.lbfa_mean_seq_workspace_bytes(n, H, T, D)
+                    ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=self.device)
+                    _lib.check(lib.lbfa_mean_seq(k.data_ptr(), code, km_new.data_ptr(), ws.data_ptr(), ws_bytes, n, H, T, D,
+                                                 _lib.strides3(k3), stream), lib)
+                else:
+                    _lib.check(lib.lbfa_kvcache_mean(k.data_ptr(), code, new_lens.data_ptr(), km_new.data_ptr(), n, H, T, D,
+                                                     _lib.strides3(k3), stream), lib)
+                rows = torch.tensor(fresh, dtype=torch.int64, device=self.device)
+                self.km.index_copy_(0, torch.tensor([slots[i] for i in fresh], dtype=torch.int64, device=self.device), km_new[rows])
+            _lib.check(lib.lbfa_kvcache_paged_append(
+                k.data_ptr(), v.data_ptr(), code, new_lens.data_ptr() if new_lens is not None else None,
+                self.km.data_ptr() if self.smooth_k else None, self.k_codes.data_ptr(), self.k_scale.data_ptr(), self.v.data_ptr(),
+                self.k_tail.data_ptr(), self.seqlens.data_ptr(), self.block_table.data_ptr(),
+                slot_t.data_ptr() if slot_t is not None else None, n, H, T, D, self.max_seqs, self.num_pages, self.page_size,
+                self.max_pages_per_seq, _lib.strides3(k3), _lib.strides3(v3), self.k_qmax, stream), lib)
+            # the kernel reads seqlens and does not advance it
+            add = torch.full((n,), T, dtype=torch.int32, device=self.device) if new_lens is None else torch.clamp(new_lens, 0, T)
+            if slot_t is None:
+                self.seqlens += add
+            else:
+                self.seqlens.index_add_(0, slot_t.long(), add)
+        return self
+
+    def free(self, slots):
+        """Give the pages of `slots` (an int or distinct ints) back to the pool; the slots are fresh again.  Returns self."""
+        import torch
+        slots = [slots] if isinstance(slots, int) else list(slots)
+        slots = _slot_list(slots, len(slots), self.max_seqs)
+        for s in slots:
+            self.allocator.release(s)
+        if slots:
+            self.seqlens.index_fill_(0, torch.tensor(slots, dtype=torch.int64, device=self.device), 0)
+        return self
+
+    def max_seqlen(self, slots=None) -> int:
+        """host upper bound of the lengths of `slots` (None: all)"""
+        return max(self.allocator.bound[s] for s in (range(self.max_seqs) if slots is None else slots))
+
+    def gather(self, slot: int):
+        """Debugging aid (torch ops, read-only): the sequence in `slot` through its block table as contiguous tensors - codes
+        int8 [Hkv, n, Dp], scales fp32 [Hkv, n / 64], V fp16 [Hkv, n, Dp], n = its pages * page_size.  Rows at or past
+        seqlens[slot] are meaningless."""
+        import torch
+        idx = torch.tensor(self.allocator.pages[slot], dtype=torch.int64, device=self.device)
+        H, D = self.num_kv_heads, self.padded_head_dim
+        # (contiguous() : with one 64-key block per page the reshape of the scales is a strided view)
+        return (self.k_codes[idx].transpose(0, 1).reshape(H, -1, D).contiguous(),
+                self.k_scale[idx].transpose(0, 1).reshape(H, -1).contiguous(),
+                self.v[idx].transpose(0, 1).reshape(H, -1, D).contiguous())
+
+
+def lowbit_fa_decode(q, cache, tensor_layout: str = "HND", is_causal: bool = False,
+                     sm_scale: Optional[float] = None, return_lse: bool = False, num_splits: int = 0, q_bits: int = 8,
+                     slots=None):
     """Attention of the new queries q [B, Hq, Sq, D] ("HND") or [B, Sq, Hq, D] ("NHD") to everything in `cache` (the keys of
     these queries appended first).  Sq * (Hq / Hkv) <= 64.  `is_causal`: bottom-right aligned, query i sees keys
     < seqlens[b] - Sq + 1 + i.  `num_splits`: key slices (0: chosen by `lbfa_decode_num_splits`); results are bitwise
     reproducible for a given value.  Returns o (shape and dtype of q) and, with `return_lse`, the natural-log LSE [B, Hq, Sq]
-    fp32.  A sequence with no keys gets zeros and -inf.  Forward only."""
+    fp32.  A sequence with no keys gets zeros and -inf.  Forward only.
+    `cache` is a `LowbitKVCache` or a `LowbitPagedKVCache`; with a paged one row b of q attends to the sequence in
+    `slots[b]` (distinct ints; None: all slots in order)."""
     ops = ops_for(q)
     if ops.name != "torch":
         raise TypeError("lowbit_fa_decode takes torch tensors")
     torch = ops.torch
-    if not isinstance(cache, LowbitKVCache):
-        raise TypeError("cache must be a LowbitKVCache")
+    paged = isinstance(cache, LowbitPagedKVCache)
+    if not paged and not isinstance(cache, LowbitKVCache):
+        raise TypeError("cache must be a LowbitKVCache or a LowbitPagedKVCache")
+    if slots is not None and not paged:
+        raise ValueError("slots address the sequences of a LowbitPagedKVCache; a LowbitKVCache is decoded as a whole batch")
     if torch.is_grad_enabled() and q.requires_grad:
         raise RuntimeError("lowbit_fa_decode is forward-only: there is no backward through the KV cache "
                            "(call it under torch.no_grad() or detach q)")
@@ -164,7 +389,9 @@ def lowbit_fa_decode(q, cache: LowbitKVCache, tensor_layout: str = "HND", is_cau
         q = q.contiguous()
     qshape = ops.shape(q)
     (B, Hq, Sq), q3 = _qpb._bhs(qshape, ops.strides(q), tensor_layout)
-    if B != cache.batch:
+    if paged:
+        slot_list = _slot_list(slots, B, cache.max_seqs)
+    elif B != cache.batch:
         raise ValueError(f"expected batch {cache.batch}, got {B}")
     o = ops.empty(qshape, q.dtype, q)
     (_, _, _), o3 = _qpb._bhs(qshape, ops.strides(o), tensor_layout)
@@ -173,9 +400,21 @@ def lowbit_fa_decode(q, cache: LowbitKVCache, tensor_layout: str = "HND", is_cau
         return (o[..., :head_dim_og], lse) if return_lse else o[..., :head_dim_og]
     lib = _lib.load()
     Hkv, D = cache.num_kv_heads, cache.padded_head_dim
-    max_k = max(1, min(cache.max_seqlen, cache.capacity))
+    max_k = max(1, min(cache.max_seqlen(slot_list), cache.allocator.capacity) if paged else min(cache.max_seqlen, cache.capacity))
     ws_bytes = lib.lbfa_decode_workspace_bytes(B, Hq, Hkv, Sq, D, max_k, int(num_splits))
     ws = ops.empty((max(ws_bytes, 16),), ops.uint8, q)
+    if paged:
+        with ops.device_guard(q):
+            slot_t = torch.tensor(slot_list, dtype=torch.int32, device=cache.device) if slots is not None else None
+            _lib.check(lib.lbfa_decode_paged(
+                q.data_ptr(), ops.dtype_code(q), cache.k_codes.data_ptr(), cache.k_scale.data_ptr(), cache.v.data_ptr(),
+                cache.km.data_ptr() if cache.km is not None else None, cache.seqlens.data_ptr(), cache.block_table.data_ptr(),
+                slot_t.data_ptr() if slot_t is not None else None, o.data_ptr(), lse.data_ptr() if return_lse else None,
+                ws.data_ptr(), ws_bytes, B, Hq, Hkv, Sq, D, cache.max_seqs, cache.num_pages, cache.page_size,
+                cache.max_pages_per_seq, max_k, int(num_splits), _lib.strides3(q3), _lib.strides3(o3), float(sm_scale),
+                127 if q_bits == 8 else 7, 1 if is_causal else 0, ops.stream(q)), lib)
+        o = o[..., :head_dim_og]
+        return (o, lse) if return_lse else o
     with ops.device_guard(q):
         _lib.check(lib.lbfa_decode(q.data_ptr(), ops.dtype_code(q), cache.k_codes.data_ptr(), cache.k_scale.data_ptr(),
                                    cache.v.data_ptr(), cache.km.data_ptr() if cache.km is not None else None,

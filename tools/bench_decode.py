@@ -7,6 +7,9 @@ Shapes: Hq 32 / Hkv 8, D 128, Sq 1, B in {1, 8, 64} x context in {4K, 32K, 128K}
 (so drift hits all alike), each step bracketed by HIP events; median and the 10th .. 90th percentile spread per arm:
   decode       `lowbit_fa_decode` on a filled `LowbitKVCache`, num_splits chosen by lbfa_decode_num_splits
   decode_1     the same with num_splits = 1
+  decode_paged      `lowbit_fa_decode` on a `LowbitPagedKVCache` holding the same keys in pages of 64 handed out in a RANDOM order:
+                    the worst case, one table look-up per tile and no locality between tiles
+  decode_paged_256  the same with pages of 256 keys
   dense_int8   the dense int8 operator at Sq = 1 on the 16-bit K / V (`lowbit_fa_qk_int8_pv_fp16_triton`): what the library offered
                for a decode step before the cache existed - it re-smooths and re-quantises K on every call
   sdpa_fp16    torch's scaled_dot_product_attention on the fp16 K / V, the Hq / Hkv query heads of a kv head as its query rows
@@ -17,8 +20,10 @@ Prints one JSON document (and writes it to --out).
 
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/bench_decode.py --calls-only [--shapes ...]
 
-`--calls-only` fills the cache and makes ten calls of `decode` and of `decode_1` per shape, untimed: the run to put under the
-profiler for per-kernel times (profiles/decode_kernel_trace.json), separate from the timed run.
+`--calls-only` fills the caches and makes ten calls of `decode`, `decode_1` and `decode_paged` per shape, untimed: the run to put
+under the profiler for per-kernel times (profiles/decode_kernel_trace.json), separate from the timed run.
+The yardstick of the paged arms is the `decode` arm of the same run: `decode_paged*_vs_decode` is the ratio of the medians and
+`decode_paged*_within_decode_p10_p90` says whether the paged median lies inside the contiguous arm's 10th .. 90th percentile band.
 """
 import argparse
 import json
@@ -42,6 +47,16 @@ def _pct(xs, p):
     return xs[min(len(xs) - 1, int(round(p * (len(xs) - 1))))]
 
 
+def _paged_cache(lb, k, v, page, seed):
+    """the keys of k, v in a paged cache whose pages are handed out in a random order"""
+    B, S = k.shape[0], k.shape[2]
+    per_seq = (S + page - 1) // page
+    g = torch.Generator()
+    g.manual_seed(seed)
+    order = torch.randperm(B * per_seq, generator=g).tolist()
+    return lb.LowbitPagedKVCache(B * per_seq, page, HKV, D, B, per_seq, torch.float16, k.device, page_order=order).append(k, v)
+
+
 def run_shape(name, B, S, steps, warmup):
     import lowbit_quant_fa2_paddle_amd as lb
     from lowbit_quant_fa2_paddle_amd import _lib
@@ -51,16 +66,20 @@ def run_shape(name, B, S, steps, warmup):
     v = torch.randn((B, HKV, S, D), device=dev, dtype=torch.float16)
     q = torch.randn((B, HQ, 1, D), device=dev, dtype=torch.float16)
     cache = lb.LowbitKVCache(B, HKV, D, S, torch.float16, dev).append(k, v)
+    paged64, paged256 = _paged_cache(lb, k, v, 64, 1), _paged_cache(lb, k, v, 256, 2)
     q_rows = q.view(B, HKV, HQ // HKV, D)  # the query heads of a kv head as query rows of one head
     arms = {
         "decode": lambda: lb.lowbit_fa_decode(q, cache),
         "decode_1": lambda: lb.lowbit_fa_decode(q, cache, num_splits=1),
+        "decode_paged": lambda: lb.lowbit_fa_decode(q, paged64),
+        "decode_paged_256": lambda: lb.lowbit_fa_decode(q, paged256),
         "dense_int8": lambda: lb.lowbit_fa_qk_int8_pv_fp16_triton(q, k, v),
         "sdpa_fp16": lambda: F.scaled_dot_product_attention(q_rows, k, v),
     }
     with torch.no_grad():
         ref = arms["sdpa_fp16"]().view(B, HQ, 1, D).float()
         err = {a: float((arms[a]().float() - ref).abs().max()) for a in ("decode", "decode_1", "dense_int8")}
+        same = {a: bool(torch.equal(arms[a](), arms["decode"]())) for a in ("decode_paged", "decode_paged_256")}
         for _ in range(warmup):
             for fn in arms.values():
                 fn()
@@ -76,13 +95,18 @@ def run_shape(name, B, S, steps, warmup):
     splits = _lib.load().lbfa_decode_num_splits(B, HKV, S)
     bytes_needed = B * HKV * (S * 3 * D + (S // 64) * 4) + 2 * B * HQ * D * 2
     rec = dict(shape=name, B=B, Hq=HQ, Hkv=HKV, Sq=1, context=S, D=D, num_splits=splits, bytes_needed=bytes_needed,
-               max_abs_diff_vs_sdpa=err)
+               max_abs_diff_vs_sdpa=err, paged_bit_identical_to_decode=same)
     for a in arms:
         rec[a + "_us"] = statistics.median(ts[a])
         rec[a + "_us_p10_p90"] = [_pct(ts[a], 0.1), _pct(ts[a], 0.9)]
     rec["decode_share_of_hbm_ceiling"] = bytes_needed / (rec["decode_us"] * 1e-6) / HBM_CEILING
     for a in ("decode_1", "dense_int8", "sdpa_fp16"):
         rec[f"speedup_vs_{a}"] = rec[a + "_us"] / rec["decode_us"]
+    lo, hi = rec["decode_us_p10_p90"]
+    for a in ("decode_paged", "decode_paged_256"):
+        rec[f"{a}_vs_decode"] = rec[a + "_us"] / rec["decode_us"]
+        rec[f"{a}_within_decode_p10_p90"] = lo <= rec[a + "_us"] <= hi
+        rec[f"{a}_slower_beyond_spread"] = rec[a + "_us_p10_p90"][0] > hi
     # faster than the dense operator by more than the run-to-run spread: its fastest decile against our slowest
     rec["beats_dense_int8_beyond_spread"] = rec["dense_int8_us_p10_p90"][0] > rec["decode_us_p10_p90"][1]
     return rec
@@ -96,9 +120,11 @@ def calls_only(B, S, calls=10):
     v = torch.randn((B, HKV, S, D), device=dev, dtype=torch.float16)
     q = torch.randn((B, HQ, 1, D), device=dev, dtype=torch.float16)
     cache = lb.LowbitKVCache(B, HKV, D, S, torch.float16, dev).append(k, v)
+    paged = _paged_cache(lb, k, v, 64, 1)
     for _ in range(calls):
         lb.lowbit_fa_decode(q, cache)
         lb.lowbit_fa_decode(q, cache, num_splits=1)
+        lb.lowbit_fa_decode(q, paged)
     torch.cuda.synchronize()
 
 
