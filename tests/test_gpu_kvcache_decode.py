@@ -137,13 +137,13 @@ def test_ragged_first_append_takes_the_mean_of_its_valid_rows(oracle, dev):
 # 5. decode equals the oracle
 # ------------------------------------------------------------------------------------------------------------------------
 def _decode_case(orc, dev, *, Sq, G, Hkv, D, layout, dtype, dist, lens, q_bits=8, k_bits=8, splits=(1, 2, 7, 0), seed=0,
-                 causal_modes=(False, True)):
+                 causal_modes=(False, True), smooth_k=True, sm_scale=None):
     import lowbit_quant_fa2_paddle_amd as lb
     rng = np.random.default_rng(seed)
     B, Hq, T = len(lens), G * Hkv, max(lens)
     Dp = 64 if D <= 64 else 128
-    sm_scale = D ** -0.5
-    cache = lb.LowbitKVCache(B, Hkv, D, T, TDT[dtype], dev, k_bits=k_bits)
+    scale_arg, sm_scale = sm_scale, D ** -0.5 if sm_scale is None else sm_scale
+    cache = lb.LowbitKVCache(B, Hkv, D, T, TDT[dtype], dev, k_bits=k_bits, smooth_k=smooth_k)
     k = _rand(orc, rng, (B, Hkv, T, D), dtype, dist, bias=0.5 if dist == "normal" else 0.0)
     v = _rand(orc, rng, (B, Hkv, T, D), dtype, "normal")
     # a prefill, then the rest token by chunk, so the open-block path feeds the decode too
@@ -162,7 +162,7 @@ def _decode_case(orc, dev, *, Sq, G, Hkv, D, layout, dtype, dist, lens, q_bits=8
     qp = np.pad(q, [(0, 0)] * 3 + [(0, Dp - D)])
     q_i8, q_scale = kr.quant_q(orc, qp, sm_scale, 127 if q_bits == 8 else 7)
     k_i8, k_scale, v16 = cache.k_codes.cpu().numpy(), cache.k_scale.cpu().numpy(), _np(cache.v)
-    corr = kr.lse_correction(orc, qp, _np(cache.km), dtype)
+    corr = kr.lse_correction(orc, qp, _np(cache.km) if smooth_k else None, dtype)
     worst = 0.0
     for causal in causal_modes:
         o_ref, lse2_ref = kr.oracle_decode(orc, q_i8, q_scale, k_i8, k_scale, v16, lens, causal=causal, out_dtype=dtype)
@@ -170,7 +170,7 @@ def _decode_case(orc, dev, *, Sq, G, Hkv, D, layout, dtype, dist, lens, q_bits=8
         for ns in splits:
             what = f"Sq{Sq} G{G} D{D} {layout} {dtype} {dist} causal={causal} splits={ns}"
             o, lse = lb.lowbit_fa_decode(tq, cache, tensor_layout=layout, is_causal=causal, return_lse=True, num_splits=ns,
-                                         q_bits=q_bits)
+                                         q_bits=q_bits, sm_scale=scale_arg)
             assert o.shape == tq.shape and o.dtype == tq.dtype and tuple(lse.shape) == (B, Hq, Sq)
             on = _np(o if layout == "HND" else o.transpose(1, 2))
             worst = max(worst, kr.check_o(on, o_ref[..., :D], dtype, what))
@@ -178,9 +178,9 @@ def _decode_case(orc, dev, *, Sq, G, Hkv, D, layout, dtype, dist, lens, q_bits=8
             dead = np.isinf(lse_ref)
             assert np.all(on[dead] == 0), what  # no visible key: zeros
             o2, lse2 = lb.lowbit_fa_decode(tq, cache, tensor_layout=layout, is_causal=causal, return_lse=True, num_splits=ns,
-                                           q_bits=q_bits)
+                                           q_bits=q_bits, sm_scale=scale_arg)
             assert torch.equal(o, o2) and torch.equal(lse, lse2), what + ": two runs differ"
-            o3 = lb.lowbit_fa_decode(tq, cache, tensor_layout=layout, is_causal=causal, num_splits=ns, q_bits=q_bits)
+            o3 = lb.lowbit_fa_decode(tq, cache, tensor_layout=layout, is_causal=causal, num_splits=ns, q_bits=q_bits, sm_scale=scale_arg)
             assert torch.equal(o, o3), what + ": O depends on return_lse"
     return worst
 
@@ -194,6 +194,10 @@ DECODE_CASES = [
     dict(Sq=4, G=8, Hkv=1, D=128, layout="NHD", dtype="bf16", dist="randint", lens=[257, 64]),         # 32 rows: 2 row blocks
     dict(Sq=16, G=4, Hkv=1, D=64, layout="HND", dtype="fp16", dist="randint", lens=[449, 2]),          # 64 rows at D = 64
     dict(Sq=1, G=1, Hkv=2, D=64, layout="HND", dtype="fp16", dist="normal", lens=[192, 65], q_bits=4, k_bits=4),
+    # geometries of tests/decode_fuzz_cases.py `PINNED`: rows that are no power of two
+    dict(Sq=5, G=4, Hkv=2, D=128, layout="HND", dtype="fp16", dist="normal", lens=[449, 2]),           # 20 rows: head 3 in two row blocks
+    dict(Sq=5, G=7, Hkv=1, D=64, layout="NHD", dtype="bf16", dist="normal", lens=[449, 2], smooth_k=False),   # 35 rows: 3 row blocks
+    dict(Sq=3, G=16, Hkv=1, D=128, layout="HND", dtype="fp16", dist="normal", lens=[449, 1], sm_scale=0.2, k_bits=4),  # 48 rows
 ]
 
 

@@ -44,12 +44,13 @@ def _nhd(t):
     return t.transpose(1, 2).contiguous()
 
 
-def _paged(dev, *, num_pages, page, Hkv, D, max_seqs, max_pages, dtype, k_bits=8, seed=0, order=None):
+def _paged(dev, *, num_pages, page, Hkv, D, max_seqs, max_pages, dtype, k_bits=8, seed=0, order=None, smooth_k=True):
     """a paged cache full of garbage whose pages come in a scrambled order"""
     import lowbit_quant_fa2_paddle_amd as lb
     if order is None:
         order = np.random.default_rng(seed).permutation(num_pages).tolist()
-    cache = lb.LowbitPagedKVCache(num_pages, page, Hkv, D, max_seqs, max_pages, TDT[dtype], dev, k_bits=k_bits, page_order=order)
+    cache = lb.LowbitPagedKVCache(num_pages, page, Hkv, D, max_seqs, max_pages, TDT[dtype], dev, k_bits=k_bits, smooth_k=smooth_k,
+                                  page_order=order)
     cache.k_codes.fill_(127)
     cache.k_scale.fill_(float("inf"))
     cache.v.fill_(float("nan"))
