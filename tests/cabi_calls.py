@@ -88,3 +88,29 @@ def check_table(lib, table):
         st, msg = call(lib, name, **overrides)
         assert st == _lib.LBFA_EINVAL, (name, overrides, st, msg)
         assert msg == message, (name, overrides, msg)
+
+
+# ---- GPU side: the same keyword callers on real device pointers -----------------------------------------------------------
+# argument order of the entry points that have no default problem above (they cannot be refused without a device)
+GPU_ORDER = {
+    "lbfa_decode": ("q", "dtype", "k_codes", "k_scale", "v_cache", "km", "seqlens", "o", "lse", "workspace", "workspace_bytes",
+                    "B", "Hq", "Hkv", "Sq", "D", "capacity", "max_k", "num_splits", "sq", "so", "sm_scale", "q_qmax", "causal",
+                    "stream"),
+    "lbfa_kvcache_paged_append": ("k_new", "v_new", "dtype", "new_lens", "km", "k_codes", "k_scale", "v_cache", "k_tail", "seqlens",
+                                  "block_table", "slots", "B", "Hkv", "T", "D", "num_slots", "num_pages", "page_size", "max_pages",
+                                  "sk", "sv", "k_qmax", "stream"),
+    "lbfa_decode_paged": ("q", "dtype", "k_codes", "k_scale", "v_cache", "km", "seqlens", "block_table", "slots", "o", "lse",
+                          "workspace", "workspace_bytes", "B", "Hq", "Hkv", "Sq", "D", "num_slots", "num_pages", "page_size",
+                          "max_pages", "max_k", "num_splits", "sq", "so", "sm_scale", "q_qmax", "causal", "stream"),
+}
+
+
+def call_gpu(lib, name, **kwargs):
+    """One launching call of `name` with EVERY argument given by keyword (the names of DEFAULTS / GPU_ORDER, any order): device
+    pointers as integers or None, stride arrays as tuples.  Nothing is taken from the default problem - its pointers are host
+    scratch - so a missing or misspelt argument is an error here, never a launch.  Raises as the front end does on a non-zero
+    status."""
+    order = tuple(DEFAULTS[name]) if name in DEFAULTS else GPU_ORDER[name]
+    assert set(kwargs) == set(order), (name, sorted(set(order) ^ set(kwargs)))
+    assert not any(isinstance(v, A) for v in kwargs.values()), name
+    _lib.check(getattr(lib, name)(*[_arg(kwargs[k]) for k in order]), lib)

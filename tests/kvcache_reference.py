@@ -91,8 +91,11 @@ class CacheRef:
                     m = np.mean(k_new[b, :, :lens[b]].astype(np.float64), axis=1).astype(np.float32)
                     self.km[b] = orc.to_storage(m, self.dtype)
         for b in range(self.B):
-            s0, tb = int(self.seqlens[b]), int(lens[b])
-            if tb == 0:
+            # the device-side clipping of `append_range` (kvcache.hip): a length outside [0, cap] is clamped, rows that would pass
+            # the capacity are dropped
+            s0 = min(max(int(self.seqlens[b]), 0), self.cap)
+            tb = min(int(lens[b]), self.cap - s0)
+            if tb <= 0:
                 continue
             end = s0 + tb
             first, last = s0 // BLKK, (end - 1) // BLKK
