@@ -1,4 +1,4 @@
-// Split-KV decode attention over the int8 KV cache (kvcache.hip) for short queries, gfx950.
+// Split-KV decode attention over the int8 KV cache (kvcache.hip), contiguous or paged, for short queries, gfx950.
 //
 // One workgroup = ONE wave = one (batch, kv head, key slice) and all M = Sq * (Hq / Hkv) <= 64 query rows that share the kv head:
 // K codes and V are streamed once per GQA group.  The kernel is HBM-bound (3 D bytes per key), so it has none of the prefill
@@ -22,6 +22,13 @@
 // Slices: tile range [split * tps, (split + 1) * tps) of the sequence's ceil(n / 64) tiles, tps = ceil(tiles / splits).  With
 // more than one slice each writes un-normalised fp32 acc and (m, l); attn_decode_combine_kernel adds them in one fixed order (no
 // atomics: bitwise reproducible for a given number of slices).
+//
+// ONE kernel body serves the contiguous cache and the paged one.  What differs - where a tile lives - is the KV policy:
+// ContiguousKV (cache [B, Hkv, cap, D], row b of the call is sequence b) or PagedKV (pool of pages behind a block table, row b
+// addresses slot slots[b]).  A policy owns the slot of the row with its clamp, the bases of codes, V and scales, fetch(t) (the
+// table load for tile t) and locate(t, pg) (the number that names the tile to the loads).  Everything else - Q prologue, masks,
+// online softmax, V staging, epilogue, partials - is written once and does not know where a tile lives (the schedule of the
+// tile loop has a form with and one without table look-ups, see there): same products in the same order per slice, so the two layouts give bit-identical results for the same number of slices.
 #include "attn_common.h"
 
 namespace lbfa {
@@ -29,20 +36,83 @@ namespace lbfa {
 typedef short s16x4v __attribute__((ext_vector_type(4)));
 constexpr float kLog2e = 1.44269504f;  // the literal of src/core.py:347; the natural-log LSE is a correctly rounded division by it
 
-template <int DT, int D, int MB>
-__global__ __launch_bounds__(64) void attn_decode_kernel(DecodeParams p) {
+// Contiguous cache: k_codes int8 / v fp16 [B, Hkv, cap, D], k_scale fp32 [B, Hkv, cap / 64].  Tile t of (b, hk) is tile t behind
+// the bases of that (b, hk); seqlens and km are indexed by the row of the call.
+struct ContiguousKV {
+  typedef DecodeParams Params;
+  typedef int tile_t;  // what names a tile to the loads, see locate()
+  static constexpr bool kTable = false;
+  int slot;
+  const int8_t* codes;
+  const unsigned short* v;
+  const float* scale;
+  __device__ __forceinline__ ContiguousKV(const Params& p, int b, int hk, int D) {
+    const int64_t bh = (int64_t)b * p.Hkv + hk;
+    slot = b;
+    codes = p.k_codes + bh * (int64_t)p.cap * D;
+    v = p.v + bh * (int64_t)p.cap * D;
+    scale = p.k_scale + bh * (p.cap >> 6);
+  }
+  __device__ __forceinline__ int fetch(int) const { return 0; }
+  __device__ __forceinline__ tile_t locate(int t, int) const { return t; }
+};
+
+// Paged cache: a pool k_codes int8 / v fp16 [num_pages, Hkv, page_size, D], k_scale fp32 [num_pages, Hkv, page_size / 64]; key j of
+// the sequence in slot s lives in page block_table[s * max_pages + j / page_size], row j % page_size.  page_size is a multiple of
+// 64, so a tile - 64 D bytes of codes, 128 D bytes of V, one scale - is contiguous inside one page.  Tile t of the sequence is
+// tile `gt` of the POOL seen as [num_pages, Hkv, page_size / 64] tiles of 64 keys: codes, V and scale of a tile are all found from
+// that one 64-bit number.  b is the ROW of the call (q, o, lse, workspace); seqlens, km and the block table belong to its slot.
+// Slot and page ids are device data the host cannot check: both are clamped into [0, num_slots) / [0, num_pages) (wave-uniform
+// scalar work), so a corrupt table gives a wrong answer, never an address outside the pool.  fetch() is the table load,
+// locate() the arithmetic on its result: the loop fetches the page id of the tile AFTER the look-ahead tile, so that no K / V
+// load waits behind a fresh table load.  All of it depends on blockIdx and the loop counter only: scalar registers, one scalar
+// divide per tile (page_size is any multiple of 64, not only a power of two).
+struct PagedKV {
+  typedef PagedDecodeParams Params;
+  typedef int64_t tile_t;
+  static constexpr bool kTable = true;
+  int slot;
+  const int8_t* codes;
+  const unsigned short* v;
+  const float* scale;
+  const int* tbl;
+  int tpp, hk, Hkv, num_pages;  // tpp: tiles per page
+  __device__ __forceinline__ PagedKV(const Params& p, int b, int hk_, int) {
+    const int sl = p.slots != nullptr ? p.slots[b] : b;
+    slot = __builtin_amdgcn_readfirstlane(min(max(sl, 0), p.num_slots - 1));
+    codes = p.k_codes;
+    v = p.v;
+    scale = p.k_scale;
+    tbl = p.block_table + (int64_t)slot * p.max_pages;
+    tpp = p.page_size >> 6;
+    hk = hk_;
+    Hkv = p.Hkv;
+    num_pages = p.num_pages;
+  }
+  __device__ __forceinline__ int fetch(int t) const { return tbl[t / tpp]; }
+  __device__ __forceinline__ tile_t locate(int t, int pg) const {
+    pg = __builtin_amdgcn_readfirstlane(min(max(pg, 0), num_pages - 1));
+    return ((int64_t)pg * Hkv + hk) * tpp + t % tpp;
+  }
+};
+
+template <class KV, int DT, int D, int MB>
+__global__ __launch_bounds__(64) void attn_decode_kernel(typename KV::Params p) {
   constexpr int KS = D / 64;        // k-steps of the score product
   constexpr int CB = D / 16;        // 16-channel blocks of O^T
   constexpr int VROW = 2 * D + 32;  // bytes per LDS row
   constexpr int VCH = D / 8;        // 16-byte chunks of a V tile per lane
+  typedef typename KV::tile_t tile_t;
   __shared__ __attribute__((aligned(16))) unsigned char smem[64 * VROW];
   const int split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
   const int lane = threadIdx.x, i16 = lane & 15, g = lane >> 4;
-  const int n = min(max(p.seqlens[b], 0), p.max_k);
+  const KV kv(p, b, hk, D);
+  const int n = min(max(p.seqlens[kv.slot], 0), p.max_k);
   const int ntiles = (n + 63) >> 6;
   const int tps = (ntiles + p.splits - 1) / p.splits;
   const int t0 = split * tps, t1 = min(t0 + tps, ntiles);
-  const int64_t bh = (int64_t)b * p.Hkv + hk;
+  const int64_t bh = (int64_t)b * p.Hkv + hk;         // (row of the call, kv head): the partials
+  const int64_t sh = (int64_t)kv.slot * p.Hkv + hk;   // (slot, kv head): km
 
   // ---- query rows of this lane: load, quantise, q . km ---------------------------------------------------------------
   int row[MB], hq[MB], sq[MB], lim[MB];
@@ -73,13 +143,13 @@ __global__ __launch_bounds__(64) void attn_decode_kernel(DecodeParams p) {
         }
         uint4 kmr[2] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
         if (p.km != nullptr) {
-          kmr[0] = *reinterpret_cast<const uint4*>(p.km + bh * D + 64 * s + 16 * g);
-          kmr[1] = *reinterpret_cast<const uint4*>(p.km + bh * D + 64 * s + 16 * g + 8);
+          kmr[0] = *reinterpret_cast<const uint4*>(p.km + sh * D + 64 * s + 16 * g);
+          kmr[1] = *reinterpret_cast<const uint4*>(p.km + sh * D + 64 * s + 16 * g + 8);
         }
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
-          // (spelled out, not elem16 / quant_codes16 as in the forward kernels: behind either helper the compiler swaps the operands
-          // of an add in this kernel's LSE epilogue, and the kernel has to stay the parent's instruction for instruction)
+          // (the text of elem16 / quant_codes16 of lbfa_common.h, spelled out: the same operations in the same order.  Moving onto
+          // the helpers changes the operand order of 16 adds in the compiled kernel and nothing else; it is a step of its own)
           const unsigned w[4] = {raw[hf].x, raw[hf].y, raw[hf].z, raw[hf].w};
           const unsigned mw[4] = {kmr[hf].x, kmr[hf].y, kmr[hf].z, kmr[hf].w};
 #pragma unroll
@@ -136,21 +206,21 @@ __global__ __launch_bounds__(64) void attn_decode_kernel(DecodeParams p) {
     for (int cb = 0; cb < CB; ++cb) acc[rb][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
 
-  const int8_t* kbase = p.k_codes + bh * (int64_t)p.cap * D + (int64_t)i16 * D + 16 * g;
-  const unsigned short* vbase = p.v + bh * (int64_t)p.cap * D;
-  const float* ksc = p.k_scale + bh * (p.cap >> 6);
+  const int8_t* kbase = kv.codes + (int64_t)i16 * D + 16 * g;
+  const unsigned short* vbase = kv.v;
+  const float* ksc = kv.scale;
   typedef __attribute__((address_space(3))) unsigned char lds_byte;
   typedef __attribute__((address_space(3))) s16x4v lds_s16x4;
   lds_byte* const vt_lane = (lds_byte*)smem + (4 * g + (i16 >> 2)) * VROW + (i16 & 3) * 8;
 
-  auto load_k = [&](int t, i32x4 (&kf)[4][KS]) __attribute__((always_inline)) {
+  auto load_k = [&](tile_t t, i32x4 (&kf)[4][KS]) __attribute__((always_inline)) {
     const int8_t* kt = kbase + (int64_t)t * 64 * D;
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
       for (int s = 0; s < KS; ++s) kf[kb][s] = *reinterpret_cast<const i32x4*>(kt + kb * 16 * D + 64 * s);
   };
-  auto load_v = [&](int t, uint4 (&vr)[VCH]) __attribute__((always_inline)) {
+  auto load_v = [&](tile_t t, uint4 (&vr)[VCH]) __attribute__((always_inline)) {
     const unsigned short* vt = vbase + (int64_t)t * 64 * D;
 #pragma unroll
     for (int u = 0; u < VCH; ++u) vr[u] = *reinterpret_cast<const uint4*>(vt + (u * 64 + lane) * 8);  // the tile is contiguous
@@ -164,8 +234,8 @@ __global__ __launch_bounds__(64) void attn_decode_kernel(DecodeParams p) {
       *reinterpret_cast<uint4*>(smem + r * VROW + ch * 16) = val;
     }
   };
-  auto compute = [&](int t, const i32x4 (&kf)[4][KS]) __attribute__((always_inline)) {
-    const float kscale = ksc[t];
+  auto compute = [&](int t, tile_t gt, const i32x4 (&kf)[4][KS]) __attribute__((always_inline)) {
+    const float kscale = ksc[gt];
 #pragma unroll
     for (int rb = 0; rb < MB; ++rb) {
       float sc[4][4];
@@ -221,43 +291,98 @@ __global__ __launch_bounds__(64) void attn_decode_kernel(DecodeParams p) {
   // ---- tile loop: K of tile t + 1 lands in the other register set, V of tile t + 1 in registers, while tile t is computed.
   // The look-ahead index is clamped to the slice (the last tile is requested twice, from cache) so no load sits in a branch.
   // 64 rows at D = 128 hold 128 accumulator registers: no room for a second tile, that instance loads and computes in turn.
+  // The schedule is written in two forms.  Without a table (ContiguousKV) a tile is named by the loop counter.  With one
+  // (PagedKV) the tile's name is carried from locate() to the loads and to compute(), and the page id of the tile after the
+  // look-ahead tile is fetched one step early.  The first is the second with fetch() = nothing and locate(t) = t, but the
+  // compiler schedules that fold differently: measured 5 % slower on one slice of 32K keys at B = 8 (801 -> 845 us), so the
+  // plain form stays for the layout that needs no table.  Everything a tile computes is in load_k / load_v / store_v / compute.
   constexpr bool AHEAD = !(MB == 4 && D == 128);
-  if constexpr (AHEAD) {
-    if (t0 < t1) {
-      i32x4 ka[4][KS], kb_[4][KS];
-      uint4 vr[VCH];
-      load_k(t0, ka);
-      load_v(t0, vr);
-      store_v(t0, vr);
-      __syncthreads();
-      for (int t = t0; t < t1; t += 2) {
-        const int ta = min(t + 1, t1 - 1);
-        load_k(ta, kb_);
-        load_v(ta, vr);
-        compute(t, ka);
+  if constexpr (!KV::kTable) {
+    if constexpr (AHEAD) {
+      if (t0 < t1) {
+        i32x4 ka[4][KS], kb_[4][KS];
+        uint4 vr[VCH];
+        load_k(t0, ka);
+        load_v(t0, vr);
+        store_v(t0, vr);
         __syncthreads();
-        if (t + 1 >= t1) break;
-        store_v(ta, vr);
+        for (int t = t0; t < t1; t += 2) {
+          const int ta = min(t + 1, t1 - 1);
+          load_k(ta, kb_);
+          load_v(ta, vr);
+          compute(t, t, ka);
+          __syncthreads();
+          if (t + 1 >= t1) break;
+          store_v(ta, vr);
+          __syncthreads();
+          const int tb = min(t + 2, t1 - 1);
+          load_k(tb, ka);
+          load_v(tb, vr);
+          compute(t + 1, t + 1, kb_);
+          __syncthreads();
+          store_v(tb, vr);
+          __syncthreads();
+        }
+      }
+    } else {
+      for (int t = t0; t < t1; ++t) {
+        i32x4 ka[4][KS];
+        uint4 vr[VCH];
+        load_k(t, ka);
+        load_v(t, vr);
+        store_v(t, vr);
         __syncthreads();
-        const int tb = min(t + 2, t1 - 1);
-        load_k(tb, ka);
-        load_v(tb, vr);
-        compute(t + 1, kb_);
-        __syncthreads();
-        store_v(tb, vr);
+        compute(t, t, ka);
         __syncthreads();
       }
     }
   } else {
-    for (int t = t0; t < t1; ++t) {
-      i32x4 ka[4][KS];
-      uint4 vr[VCH];
-      load_k(t, ka);
-      load_v(t, vr);
-      store_v(t, vr);
-      __syncthreads();
-      compute(t, ka);
-      __syncthreads();
+    if constexpr (AHEAD) {
+      if (t0 < t1) {
+        i32x4 ka[4][KS], kb_[4][KS];
+        uint4 vr[VCH];
+        tile_t ga = kv.locate(t0, kv.fetch(t0)), gb;
+        int pn = kv.fetch(min(t0 + 1, t1 - 1));  // page id of the NEXT look-ahead tile, on its way one step early
+        load_k(ga, ka);
+        load_v(ga, vr);
+        store_v(t0, vr);
+        __syncthreads();
+        for (int t = t0; t < t1; t += 2) {
+          const int ta = min(t + 1, t1 - 1);
+          gb = kv.locate(ta, pn);
+          pn = kv.fetch(min(t + 2, t1 - 1));
+          load_k(gb, kb_);
+          load_v(gb, vr);
+          compute(t, ga, ka);
+          __syncthreads();
+          if (t + 1 >= t1) break;
+          store_v(ta, vr);
+          __syncthreads();
+          const int tb = min(t + 2, t1 - 1);
+          ga = kv.locate(tb, pn);
+          pn = kv.fetch(min(t + 3, t1 - 1));
+          load_k(ga, ka);
+          load_v(ga, vr);
+          compute(t + 1, gb, kb_);
+          __syncthreads();
+          store_v(tb, vr);
+          __syncthreads();
+        }
+      }
+    } else {
+      int pn = t0 < t1 ? kv.fetch(t0) : 0;
+      for (int t = t0; t < t1; ++t) {
+        i32x4 ka[4][KS];
+        uint4 vr[VCH];
+        const tile_t ga = kv.locate(t, pn);
+        pn = kv.fetch(min(t + 1, t1 - 1));
+        load_k(ga, ka);
+        load_v(ga, vr);
+        store_v(t, vr);
+        __syncthreads();
+        compute(t, ga, ka);
+        __syncthreads();
+      }
     }
   }
 
@@ -360,7 +485,7 @@ __global__ __launch_bounds__(256) void attn_decode_combine_kernel(DecodeParams p
   }
 }
 
-// the second launch of a call with more than one slice; the paged kernel (attn_paged_decode.hip) leaves the same partials
+// the second launch of a call with more than one slice, whichever the layout of the cache
 hipError_t launch_attn_decode_combine(const DecodeParams& p, int dtype, int D, hipStream_t stream) {
   dim3 g2(p.M, p.Hkv, p.B);
 #define LBFA_CMB(DT, DD) hipLaunchKernelGGL((attn_decode_combine_kernel<DT, DD>), g2, dim3(256), 0, stream, p)
@@ -370,11 +495,12 @@ hipError_t launch_attn_decode_combine(const DecodeParams& p, int dtype, int D, h
   return hipGetLastError();
 }
 
-// ---- host-side launcher (called from lbfa_api.hip) -----------------------------------------------------------------------
-hipError_t launch_attn_decode(const DecodeParams& p, int dtype, int D, hipStream_t stream) {
+// ---- host-side launchers (called from lbfa_api.hip) ----------------------------------------------------------------------
+template <class KV>
+static hipError_t launch_decode(const typename KV::Params& p, int dtype, int D, hipStream_t stream) {
   dim3 grid(p.splits, p.Hkv, p.B);
   const int mb = (p.M + 15) / 16;
-#define LBFA_DEC(DT, DD, MB) hipLaunchKernelGGL((attn_decode_kernel<DT, DD, MB>), grid, dim3(64), 0, stream, p)
+#define LBFA_DEC(DT, DD, MB) hipLaunchKernelGGL((attn_decode_kernel<KV, DT, DD, MB>), grid, dim3(64), 0, stream, p)
 #define LBFA_DEC1(DT, DD)                 \
   do {                                    \
     if (mb <= 1) LBFA_DEC(DT, DD, 1);     \
@@ -387,7 +513,13 @@ hipError_t launch_attn_decode(const DecodeParams& p, int dtype, int D, hipStream
 #undef LBFA_DEC
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || p.splits == 1) return e;
-  return launch_attn_decode_combine(p, dtype, D, stream);
+  return launch_attn_decode_combine(p, dtype, D, stream);  // the partials are indexed by row of the call: nothing paged in them
+}
+hipError_t launch_attn_decode(const DecodeParams& p, int dtype, int D, hipStream_t stream) {
+  return launch_decode<ContiguousKV>(p, dtype, D, stream);
+}
+hipError_t launch_attn_paged_decode(const PagedDecodeParams& p, int dtype, int D, hipStream_t stream) {
+  return launch_decode<PagedKV>(p, dtype, D, stream);
 }
 
 }  // namespace lbfa

@@ -12,42 +12,79 @@
 // behind a barrier - stores the rows of block `last` to k_tail when that block stays open.  No other workgroup touches k_tail, so
 // any T from one token to a whole prompt is race-free and scheduling cannot change the result.  Workgroup x >= 1 takes the middle
 // block first + x (whole 64 new rows, never open).  V rows are cast to fp16 by the workgroup that owns their block.
+//
+// ONE kernel body writes the contiguous cache and the paged one; where a 64-key block lives is the policy's (ContiguousDst /
+// PagedDst): the slot a row of the call addresses with its range test, and the block's place with - paged - the page look-up
+// and its range test.  seqlens, k_tail and km are indexed by SLOT, k_new / v_new / new_lens by ROW of the call.
 // Built with -ffp-contract=off and correctly rounded fp32 division, as the quantiser is.
 #include "lbfa_common.h"
 
 namespace lbfa {
 
-// lengths of one sequence, clipped so that nothing is written past the capacity
-__device__ __forceinline__ void append_range(const AppendParams& p, int b, int& s0, int& tb) {
-  s0 = min(max(p.seqlens[b], 0), p.cap);
+// lengths of the sequence in slot sl that row b of the call appends to, clipped so that nothing is written past the capacity
+// (paged: cap = max_pages * page_size)
+__device__ __forceinline__ void append_range(const AppendParams& p, int b, int sl, int& s0, int& tb) {
+  s0 = min(max(p.seqlens[sl], 0), p.cap);
   tb = p.new_lens != nullptr ? min(max(p.new_lens[b], 0), p.T) : p.T;
   tb = min(tb, p.cap - s0);
 }
 
-template <int DT, int D>
-__global__ __launch_bounds__(256) void kvcache_append_kernel(AppendParams p) {
+// Contiguous cache [B, Hkv, cap, D] (scales [B, Hkv, cap / 64]): row b of the call is sequence b, block blk of (b, h) is block
+// (b * Hkv + h) * (cap / 64) + blk of the cache seen as 64-key blocks.
+struct ContiguousDst {
+  typedef AppendParams Params;
+  static __device__ __forceinline__ bool slot(const Params&, int b, int& sl) {
+    sl = b;
+    return true;
+  }
+  static __device__ __forceinline__ bool block(const Params& p, int sl, int h, int blk, int64_t& gb) {
+    gb = ((int64_t)sl * p.Hkv + h) * (p.cap >> 6) + blk;
+    return true;
+  }
+};
+// Pool of pages: k_codes int8 / v fp16 [num_pages, Hkv, page_size, D], k_scale fp32 [num_pages, Hkv, page_size / 64]; block blk of
+// the sequence in slot sl lives in page block_table[sl * max_pages + blk / (page_size / 64)].  page_size is a multiple of 64, so a
+// quantiser block never straddles two pages.  Row b addresses slot slots[b], or b when slots is null.  Slot and page ids are
+// device data the host cannot check: a row whose slot is outside [0, num_slots) is skipped, and so is a block whose page is
+// outside [0, num_pages) - workgroup-uniform scalar tests; no address is ever formed from such an id.
+struct PagedDst {
+  typedef PagedAppendParams Params;
+  static __device__ __forceinline__ bool slot(const Params& p, int b, int& sl) {
+    sl = p.slots != nullptr ? p.slots[b] : b;
+    return sl >= 0 && sl < p.num_slots;
+  }
+  static __device__ __forceinline__ bool block(const Params& p, int sl, int h, int blk, int64_t& gb) {
+    const int bpp = p.page_size >> 6;  // 64-key blocks per page
+    const int pg = p.block_table[(int64_t)sl * p.max_pages + blk / bpp];
+    if (pg < 0 || pg >= p.num_pages) return false;
+    gb = ((int64_t)pg * p.Hkv + h) * bpp + blk % bpp;  // block of the pool [num_pages, Hkv, page_size / 64]
+    return true;
+  }
+};
+
+template <class Dst, int DT, int D>
+__global__ __launch_bounds__(256) void kvcache_append_kernel(typename Dst::Params p) {
   constexpr int CPR = D / 8;       // 16-byte chunks per row
   constexpr int RPP = 256 / CPR;   // rows per pass
   constexpr int NP = 64 / RPP;     // passes per 64-key block
   __shared__ float wmax[4];
   const int x = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
   const int t = threadIdx.x, c = t % CPR, rl = t / CPR;
-  int s0, tb;
-  append_range(p, b, s0, tb);
+  int sl, s0, tb;
+  if (!Dst::slot(p, b, sl)) return;  // workgroup-uniform
+  append_range(p, b, sl, s0, tb);
   if (tb <= 0) return;  // workgroup-uniform
   const int first = s0 >> 6, last = (s0 + tb - 1) >> 6;
   if (x > 0 && first + x >= last) return;
-  const int64_t bh = (int64_t)b * p.Hkv + h;
+  const int64_t sh = (int64_t)sl * p.Hkv + h;  // (slot, head): k_tail, km
   const unsigned short* knew = p.k_new + (int64_t)b * p.kb + (int64_t)h * p.kh + c * 8;
   const unsigned short* vnew = p.v_new + (int64_t)b * p.vb + (int64_t)h * p.vh + c * 8;
-  unsigned short* tail = p.k_tail + bh * 64 * D + c * 8;
-  int8_t* codes = p.k_codes + bh * (int64_t)p.cap * D + c * 8;
-  unsigned short* vdst = p.v + bh * (int64_t)p.cap * D + c * 8;
+  unsigned short* tail = p.k_tail + sh * 64 * D + c * 8;
   float mean[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) mean[i] = 0.f;
   const bool has_mean = p.km != nullptr;
-  if (has_mean) unpack8<DT>(*reinterpret_cast<const uint4*>(p.km + bh * D + c * 8), mean);
+  if (has_mean) unpack8<DT>(*reinterpret_cast<const uint4*>(p.km + sh * D + c * 8), mean);
   const int end = s0 + tb;
 
   // x = 0: block `first`, then block `last` when it is another one; x >= 1: one middle block
@@ -55,6 +92,10 @@ __global__ __launch_bounds__(256) void kvcache_append_kernel(AppendParams p) {
   for (int pass = 0; pass < npass; ++pass) {
     const int blk = x > 0 ? first + x : (pass == 0 ? first : last);
     const int r0 = blk << 6;
+    int64_t gb;
+    if (!Dst::block(p, sl, h, blk, gb)) continue;     // workgroup-uniform, before the barriers of the pass: the block is skipped
+    int8_t* codes = p.k_codes + gb * 64 * D + c * 8;  // row r0 of the sequence
+    unsigned short* vdst = p.v + gb * 64 * D + c * 8;
     uint4 raw[NP];
 #pragma unroll
     for (int ps = 0; ps < NP; ++ps) {
@@ -83,7 +124,7 @@ __global__ __launch_bounds__(256) void kvcache_append_kernel(AppendParams p) {
     if ((t & 63) == 0) wmax[t >> 6] = amax;
     __syncthreads();  // also: every read of k_tail (pass 0) is done before pass 1 stores to it
     const float scale = block_scale(amax_collect(wmax), p.qmax);
-    if (t == 0) p.k_scale[bh * (p.cap >> 6) + blk] = scale;
+    if (t == 0) p.k_scale[gb] = scale;
     const bool open = (blk == last) && (end & 63) != 0;  // this block is the open one afterwards: keep its raw rows
 #pragma unroll
     for (int ps = 0; ps < NP; ++ps) {
@@ -91,12 +132,12 @@ __global__ __launch_bounds__(256) void kvcache_append_kernel(AppendParams p) {
       int q[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) q[i] = quant_code<false>(xs[ps][i], scale, 0.f);  // the plain division
-      if (row < end) *reinterpret_cast<uint2*>(codes + (int64_t)row * D) = pack8_i8(q);
+      if (row < end) *reinterpret_cast<uint2*>(codes + (int64_t)(row - r0) * D) = pack8_i8(q);
       if (row >= s0 && row < end) {
         if (open) *reinterpret_cast<uint4*>(tail + (int64_t)(row - r0) * D) = raw[ps];
         u32x4 vr = *reinterpret_cast<const u32x4*>(vnew + (int64_t)(row - s0) * p.vs);
         if constexpr (DT == LBFA_BF16) vr = bf16x8_to_f16x8(vr);
-        *reinterpret_cast<u32x4*>(vdst + (int64_t)row * D) = vr;
+        *reinterpret_cast<u32x4*>(vdst + (int64_t)(row - r0) * D) = vr;
       }
     }
     __syncthreads();  // wmax is reused by the second pass
@@ -136,19 +177,26 @@ __global__ __launch_bounds__(256) void kvcache_mean_kernel(RaggedMeanParams p) {
 }
 
 // ---- host-side launchers (called from lbfa_api.hip) ---------------------------------------------------------------
-int kvcache_append_grid_x(int T) {
+static int kvcache_append_grid_x(int T) {
   // T rows starting anywhere in a block touch at most (T + 126) / 64 blocks; workgroup 0 takes the first and the last
   const int touched = (T + 126) / 64;
   return touched > 2 ? touched - 1 : 1;
 }
 
-hipError_t launch_kvcache_append(const AppendParams& p, int dtype, int D, hipStream_t stream) {
+template <class Dst>
+static hipError_t launch_append(const typename Dst::Params& p, int dtype, int D, hipStream_t stream) {
   dim3 grid(kvcache_append_grid_x(p.T), p.Hkv, p.B);
-#define LBFA_APP(DT, DD) hipLaunchKernelGGL((kvcache_append_kernel<DT, DD>), grid, dim3(256), 0, stream, p)
+#define LBFA_APP(DT, DD) hipLaunchKernelGGL((kvcache_append_kernel<Dst, DT, DD>), grid, dim3(256), 0, stream, p)
   if (dtype == LBFA_F16) { if (D == 64) LBFA_APP(LBFA_F16, 64); else LBFA_APP(LBFA_F16, 128); }
   else { if (D == 64) LBFA_APP(LBFA_BF16, 64); else LBFA_APP(LBFA_BF16, 128); }
 #undef LBFA_APP
   return hipGetLastError();
+}
+hipError_t launch_kvcache_append(const AppendParams& p, int dtype, int D, hipStream_t stream) {
+  return launch_append<ContiguousDst>(p, dtype, D, stream);
+}
+hipError_t launch_kvcache_paged_append(const PagedAppendParams& p, int dtype, int D, hipStream_t stream) {
+  return launch_append<PagedDst>(p, dtype, D, stream);
 }
 
 hipError_t launch_kvcache_mean(const RaggedMeanParams& p, int dtype, int B, int D, hipStream_t stream) {

@@ -23,12 +23,11 @@ hipError_t launch_cast_bf16_f16(const void* src, void* dst, int B, int H, int S,
 hipError_t launch_absmax(const void* x, int dtype, float* out, int B, int H, int S, int D, const int64_t* st, hipStream_t stream);
 // defined in attn_bwd.hip
 hipError_t launch_attn_bwd(const BwdParams& p, int dtype, bool quant, bool causal, hipStream_t stream);
-// defined in kvcache.hip / attn_decode.hip
+// defined in kvcache.hip / attn_decode.hip: one kernel body each, instantiated for the contiguous and for the paged cache
 hipError_t launch_kvcache_append(const AppendParams& p, int dtype, int D, hipStream_t stream);
+hipError_t launch_kvcache_paged_append(const PagedAppendParams& p, int dtype, int D, hipStream_t stream);
 hipError_t launch_kvcache_mean(const RaggedMeanParams& p, int dtype, int B, int D, hipStream_t stream);
 hipError_t launch_attn_decode(const DecodeParams& p, int dtype, int D, hipStream_t stream);
-// defined in kvcache_paged.hip / attn_paged_decode.hip
-hipError_t launch_kvcache_paged_append(const PagedAppendParams& p, int dtype, int D, hipStream_t stream);
 hipError_t launch_attn_paged_decode(const PagedDecodeParams& p, int dtype, int D, hipStream_t stream);
 }  // namespace lbfa
 
@@ -924,15 +923,171 @@ int lbfa_backward_varlen(const void* q, const void* k, const void* v, const void
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// int8 KV cache and split-KV decode attention (kvcache.hip, attn_decode.hip)
+// int8 KV cache and split-KV decode attention (kvcache.hip, attn_decode.hip), over a contiguous cache [B, Hkv, capacity, D] or a
+// pool of pages behind a block table.  An append and a decode call are described once each: the paged entry points state the
+// pool (Pool::paged) and the two phrases of their messages that differ, everything else is the same checks in the same order.
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 constexpr int kDecodeMaxRows = 64;     // query rows per kv head one decode workgroup serves
 constexpr int kDecodeWaves = 1024;     // workgroups (one wave each) that fill the part: 256 CUs x 4 SIMDs
 constexpr int kDecodeMinTiles = 4;     // no key slice shorter than 4 tiles of 64 keys
 constexpr int kDecodeMaxSplits = 256;
-int check_capacity(const char* who, int cap) {
-  return cap > 0 && cap % LBFA_BLKK == 0 ? 0 : fail(LBFA_EINVAL, "%s: capacity must be a positive multiple of 64, got %d", who, cap);
+
+// Where the keys live.  Contiguous: {false, capacity}.  Paged: {true, 0, the pool}; check_pool sets cap = max_pages * page_size.
+struct Pool {
+  bool paged;
+  int cap;  // the most keys a sequence can hold
+  lbfa::PoolParams at;
+};
+int check_pool(const char* who, int B, Pool& k) {
+  const lbfa::PoolParams& a = k.at;
+  if (!k.paged)
+    return k.cap > 0 && k.cap % LBFA_BLKK == 0 ? 0 : fail(LBFA_EINVAL, "%s: capacity must be a positive multiple of 64, got %d", who, k.cap);
+  if (a.page_size <= 0 || a.page_size % LBFA_BLKK != 0)
+    return fail(LBFA_EINVAL, "%s: page_size must be a positive multiple of 64, got %d", who, a.page_size);
+  if (a.num_pages < 1 || a.num_slots < 1 || a.max_pages < 1)
+    return fail(LBFA_EINVAL, "%s: num_pages, num_slots and max_pages_per_seq must be at least 1, got %d, %d and %d", who, a.num_pages,
+                a.num_slots, a.max_pages);
+  if ((int64_t)a.max_pages * a.page_size > 0x7fffffffLL)
+    return fail(LBFA_EINVAL, "%s: max_pages_per_seq * page_size must stay below 2^31 keys", who);
+  if (B > a.num_slots) return fail(LBFA_EINVAL, "%s: B (%d) exceeds num_slots (%d)", who, B, a.num_slots);
+  k.cap = a.max_pages * a.page_size;
+  return 0;
+}
+bool pool_aligned(const Pool& k) { return aligned(k.at.block_table, 4) && aligned(k.at.slots, 4); }
+
+struct AppendCall {
+  const char* who;
+  Operand k_new, v_new;
+  int dtype;
+  const int32_t* new_lens;
+  const void* km;
+  int8_t* k_codes;
+  float* k_scale;
+  void *v_cache, *k_tail;
+  const int32_t* seqlens;
+  int B, Hkv, T, D, k_qmax;
+  Pool pool;
+};
+// what both append entry points state, in the order of their signatures; `pool` says where the keys live
+AppendCall append_call(const char* who, const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
+                       int8_t* k_codes, float* k_scale, void* v_cache, void* k_tail, const int32_t* seqlens, int B, int Hkv, int T,
+                       int D, const int64_t strides_k[3], const int64_t strides_v[3], int k_qmax, const Pool& pool) {
+  AppendCall c{};
+  c.who = who; c.k_new = dense(k_new, strides_k); c.v_new = dense(v_new, strides_v); c.dtype = dtype;
+  c.new_lens = new_lens; c.km = km; c.k_codes = k_codes; c.k_scale = k_scale; c.v_cache = v_cache; c.k_tail = k_tail;
+  c.seqlens = seqlens; c.B = B; c.Hkv = Hkv; c.T = T; c.D = D; c.k_qmax = k_qmax; c.pool = pool;
+  return c;
+}
+int check_append(AppendCall& c) {
+  const char* who = c.who;
+  if (!c.k_new.p || !c.v_new.p || !c.k_codes || !c.k_scale || !c.v_cache || !c.k_tail || !c.seqlens || (c.pool.paged && !c.pool.at.block_table))
+    return fail(LBFA_EINVAL, "%s: null pointer", who);
+  if (c.B <= 0 || c.Hkv <= 0 || c.T <= 0) return fail(LBFA_EINVAL, "%s: empty tensor", who);
+  if (int st = check_head_dim(c.D, false)) return st;
+  if (int st = check_pool(who, c.B, c.pool)) return st;
+  if (int st = check_dtype(c.dtype)) return st;
+  if (int st = check_qmax(who, "k_qmax", c.k_qmax)) return st;
+  if (int st = check_input16(who, "k_new", c.k_new)) return st;
+  if (int st = check_input16(who, "v_new", c.v_new)) return st;
+  if (!aligned(c.k_codes, 16) || !aligned(c.v_cache, 16) || !aligned(c.k_tail, 16) || !aligned(c.km, 16) || !aligned(c.k_scale, 4) ||
+      !aligned(c.seqlens, 4) || !aligned(c.new_lens, 4) || !pool_aligned(c.pool))
+    return fail(LBFA_EINVAL, "%s: cache tensors and km must be 16-byte aligned, k_scale / seqlens / new_lens%s 4-byte aligned", who,
+                c.pool.paged ? " / block_table / slots" : "");
+  if (c.B > 65535 || c.Hkv > 65535) return fail(LBFA_EINVAL, "%s: grid too large", who);
+  return 0;
+}
+void fill_append(lbfa::AppendParams& p, const AppendCall& c) {
+  p.k_new = (const unsigned short*)c.k_new.p; p.v_new = (const unsigned short*)c.v_new.p;
+  p.new_lens = c.new_lens; p.km = (const unsigned short*)c.km;
+  p.k_codes = c.k_codes; p.k_scale = c.k_scale; p.v = (unsigned short*)c.v_cache; p.k_tail = (unsigned short*)c.k_tail;
+  p.seqlens = c.seqlens;
+  p.kb = c.k_new.st[0]; p.kh = c.k_new.st[1]; p.ks = c.k_new.st[2];
+  p.vb = c.v_new.st[0]; p.vh = c.v_new.st[1]; p.vs = c.v_new.st[2];
+  p.B = c.B; p.Hkv = c.Hkv; p.T = c.T; p.cap = c.pool.cap;
+  p.qmax = (float)c.k_qmax;
+}
+
+struct DecodeCall {
+  const char* who;
+  Operand q, o;
+  int dtype;
+  const int8_t* k_codes;
+  const float* k_scale;
+  const void *v_cache, *km;
+  const int32_t* seqlens;
+  float* lse;
+  void* workspace;
+  size_t workspace_bytes;
+  int B, Hq, Hkv, Sq, D, max_seqlen_k, num_splits;
+  double sm_scale;
+  int q_qmax, is_causal;
+  Pool pool;
+  int splits;  // set by check_decode: num_splits, or the split rule's choice
+};
+DecodeCall decode_call(const char* who, const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const void* v_cache,
+                       const void* km, const int32_t* seqlens, void* o, float* lse, void* workspace, size_t workspace_bytes, int B,
+                       int Hq, int Hkv, int Sq, int D, int max_seqlen_k, int num_splits, const int64_t strides_q[3],
+                       const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, const Pool& pool) {
+  DecodeCall c{};
+  c.who = who; c.q = dense(q, strides_q); c.o = dense(o, strides_o); c.dtype = dtype;
+  c.k_codes = k_codes; c.k_scale = k_scale; c.v_cache = v_cache; c.km = km; c.seqlens = seqlens; c.lse = lse;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.B = B; c.Hq = Hq; c.Hkv = Hkv; c.Sq = Sq; c.D = D; c.max_seqlen_k = max_seqlen_k; c.num_splits = num_splits;
+  c.sm_scale = sm_scale; c.q_qmax = q_qmax; c.is_causal = is_causal; c.pool = pool;
+  return c;
+}
+int check_decode(DecodeCall& c) {
+  const char* who = c.who;
+  if (!c.q.p || !c.o.p || !c.k_codes || !c.k_scale || !c.v_cache || !c.seqlens || (c.pool.paged && !c.pool.at.block_table))
+    return fail(LBFA_EINVAL, "%s: null pointer", who);
+  if (c.B <= 0 || c.Hq <= 0 || c.Hkv <= 0 || c.Sq <= 0) return fail(LBFA_EINVAL, "%s: empty tensor", who);
+  if (int st = check_head_dim(c.D, false)) return st;
+  if (int st = check_gqa(c.Hq, c.Hkv)) return st;
+  const int64_t M = (int64_t)c.Sq * (c.Hq / c.Hkv);
+  if (M > kDecodeMaxRows)
+    return fail(LBFA_EINVAL, "%s: Sq * (Hq / Hkv) = %lld query rows per kv head, the limit is %d (longer queries belong on the dense operator)",
+                who, (long long)M, kDecodeMaxRows);
+  if (int st = check_pool(who, c.B, c.pool)) return st;
+  if (c.max_seqlen_k < 1 || c.max_seqlen_k > c.pool.cap)
+    return c.pool.paged ? fail(LBFA_EINVAL, "%s: max_seqlen_k must be in [1, max_pages_per_seq * page_size], got %d (limit %d)", who,
+                               c.max_seqlen_k, c.pool.cap)
+                        : fail(LBFA_EINVAL, "%s: max_seqlen_k must be in [1, capacity], got %d (capacity %d)", who, c.max_seqlen_k, c.pool.cap);
+  if (c.num_splits < 0 || c.num_splits > 65535) return fail(LBFA_EINVAL, "%s: num_splits must be in [0, 65535] (0: chosen by lbfa_decode_num_splits), got %d", who, c.num_splits);
+  if (int st = check_dtype(c.dtype)) return st;
+  if (int st = check_qmax(who, "q_qmax", c.q_qmax)) return st;
+  if (!(c.sm_scale > 0.0)) return fail(LBFA_EINVAL, "%s: sm_scale must be positive", who);
+  if (int st = check_input16(who, "q", c.q)) return st;
+  if (!aligned(c.o, 8, 4)) return fail(LBFA_EINVAL, "%s: o must be 8-byte aligned with strides that are multiples of 4 elements", who);
+  if (!aligned(c.k_codes, 16) || !aligned(c.v_cache, 16) || !aligned(c.km, 16) || !aligned(c.k_scale, 4) || !aligned(c.seqlens, 4) ||
+      !pool_aligned(c.pool) || !aligned(c.lse, 4))
+    return fail(LBFA_EINVAL, "%s: cache tensors and km must be 16-byte aligned, k_scale / seqlens%s / lse 4-byte aligned", who,
+                c.pool.paged ? " / block_table / slots" : "");
+  c.splits = c.num_splits ? c.num_splits : lbfa_decode_num_splits(c.B, c.Hkv, c.max_seqlen_k);
+  if (const size_t need = lbfa_decode_workspace_bytes(c.B, c.Hq, c.Hkv, c.Sq, c.D, c.max_seqlen_k, c.splits)) {
+    if (int st = check_workspace(who, c.workspace, c.workspace_bytes, need)) return st;
+    if (!c.workspace) return fail(LBFA_EINVAL, "%s: null pointer", who);
+  }
+  if (c.B > 65535 || c.Hkv > 65535) return fail(LBFA_EINVAL, "%s: grid too large", who);
+  return 0;
+}
+void fill_decode(lbfa::DecodeParams& p, const DecodeCall& c) {
+  const int M = c.Sq * (c.Hq / c.Hkv);
+  p.q = (const unsigned short*)c.q.p; p.k_codes = c.k_codes; p.k_scale = c.k_scale; p.v = (const unsigned short*)c.v_cache;
+  p.km = c.lse ? (const unsigned short*)c.km : nullptr;  // km only enters the LSE correction
+  p.seqlens = c.seqlens; p.o = const_cast<void*>(c.o.p); p.lse = c.lse;
+  p.qb = c.q.st[0]; p.qh = c.q.st[1]; p.qs = c.q.st[2];
+  p.ob = c.o.st[0]; p.oh = c.o.st[1]; p.os = c.o.st[2];
+  p.B = c.B; p.Hq = c.Hq; p.Hkv = c.Hkv; p.Sq = c.Sq; p.group = c.Hq / c.Hkv; p.M = M;
+  p.cap = c.pool.cap; p.max_k = c.max_seqlen_k; p.splits = c.splits; p.causal = c.is_causal ? 1 : 0;
+  p.q_sm_scale = (float)(c.sm_scale * 1.44269504);  // ONE rounding of the double product, as lbfa_forward
+  p.q_qmax = (float)c.q_qmax;
+  p.corr_scale = (float)c.sm_scale;
+  if (c.splits > 1) {
+    const size_t rows = (size_t)c.B * c.Hkv * c.splits * (size_t)M;
+    p.ws_acc = (float*)c.workspace;
+    p.ws_ml = (float*)((char*)c.workspace + align256(rows * c.D * sizeof(float)));
+  }
 }
 }  // namespace
 
@@ -958,31 +1113,31 @@ int lbfa_kvcache_append(const void* k_new, const void* v_new, int dtype, const i
                         int8_t* k_codes, float* k_scale, void* v_cache, void* k_tail, const int32_t* seqlens,
                         int B, int Hkv, int T, int D, int capacity, const int64_t strides_k[3], const int64_t strides_v[3],
                         int k_qmax, void* stream) {
-  const char* who = "lbfa_kvcache_append";
-  const Operand tk = dense(k_new, strides_k), tv = dense(v_new, strides_v);
-  if (!tk.p || !tv.p || !k_codes || !k_scale || !v_cache || !k_tail || !seqlens) return fail(LBFA_EINVAL, "%s: null pointer", who);
-  if (B <= 0 || Hkv <= 0 || T <= 0) return fail(LBFA_EINVAL, "%s: empty tensor", who);
-  if (int st = check_head_dim(D, false)) return st;
-  if (int st = check_capacity(who, capacity)) return st;
-  if (int st = check_dtype(dtype)) return st;
-  if (int st = check_qmax(who, "k_qmax", k_qmax)) return st;
-  if (int st = check_input16(who, "k_new", tk)) return st;
-  if (int st = check_input16(who, "v_new", tv)) return st;
-  if (!aligned(k_codes, 16) || !aligned(v_cache, 16) || !aligned(k_tail, 16) || !aligned(km, 16) || !aligned(k_scale, 4) ||
-      !aligned(seqlens, 4) || !aligned(new_lens, 4))
-    return fail(LBFA_EINVAL, "%s: cache tensors and km must be 16-byte aligned, k_scale / seqlens / new_lens 4-byte aligned", who);
-  if (B > 65535 || Hkv > 65535) return fail(LBFA_EINVAL, "%s: grid too large", who);
+  AppendCall c = append_call("lbfa_kvcache_append", k_new, v_new, dtype, new_lens, km, k_codes, k_scale, v_cache, k_tail, seqlens,
+                             B, Hkv, T, D, strides_k, strides_v, k_qmax, Pool{false, capacity, {}});
+  if (int st = check_append(c)) return st;
   lbfa::AppendParams p{};
-  p.k_new = (const unsigned short*)k_new; p.v_new = (const unsigned short*)v_new;
-  p.new_lens = new_lens; p.km = (const unsigned short*)km;
-  p.k_codes = k_codes; p.k_scale = k_scale; p.v = (unsigned short*)v_cache; p.k_tail = (unsigned short*)k_tail;
-  p.seqlens = seqlens;
-  p.kb = tk.st[0]; p.kh = tk.st[1]; p.ks = tk.st[2];
-  p.vb = tv.st[0]; p.vh = tv.st[1]; p.vs = tv.st[2];
-  p.B = B; p.Hkv = Hkv; p.T = T; p.cap = capacity;
-  p.qmax = (float)k_qmax;
+  fill_append(p, c);
   g_err[0] = 0;
   return check_hip(lbfa::launch_kvcache_append(p, dtype, D, (hipStream_t)stream), "lbfa_kvcache_append launch");
+}
+
+int lbfa_kvcache_paged_append(const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
+                              int8_t* k_codes, float* k_scale, void* v_cache, void* k_tail, const int32_t* seqlens,
+                              const int32_t* block_table, const int32_t* slots, int B, int Hkv, int T, int D, int num_slots,
+                              int num_pages, int page_size, int max_pages_per_seq, const int64_t strides_k[3],
+                              const int64_t strides_v[3], int k_qmax, void* stream) {
+  lbfa::PoolParams at{};
+  at.block_table = block_table; at.slots = slots;
+  at.num_slots = num_slots; at.num_pages = num_pages; at.page_size = page_size; at.max_pages = max_pages_per_seq;
+  AppendCall c = append_call("lbfa_kvcache_paged_append", k_new, v_new, dtype, new_lens, km, k_codes, k_scale, v_cache, k_tail,
+                             seqlens, B, Hkv, T, D, strides_k, strides_v, k_qmax, Pool{true, 0, at});
+  if (int st = check_append(c)) return st;
+  lbfa::PagedAppendParams p{};
+  fill_append(p, c);
+  static_cast<lbfa::PoolParams&>(p) = c.pool.at;
+  g_err[0] = 0;
+  return check_hip(lbfa::launch_kvcache_paged_append(p, dtype, D, (hipStream_t)stream), "lbfa_kvcache_paged_append launch");
 }
 
 // The split rule: as many key slices as it takes for B * Hkv * slices one-wave workgroups to reach 1024 (four per CU), but no
@@ -1012,106 +1167,14 @@ int lbfa_decode(const void* q, int dtype, const int8_t* k_codes, const float* k_
                 const int32_t* seqlens, void* o, float* lse, void* workspace, size_t workspace_bytes,
                 int B, int Hq, int Hkv, int Sq, int D, int capacity, int max_seqlen_k, int num_splits,
                 const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream) {
-  const char* who = "lbfa_decode";
-  const Operand tq = dense(q, strides_q), to = dense(o, strides_o);
-  if (!tq.p || !to.p || !k_codes || !k_scale || !v_cache || !seqlens) return fail(LBFA_EINVAL, "%s: null pointer", who);
-  if (B <= 0 || Hq <= 0 || Hkv <= 0 || Sq <= 0) return fail(LBFA_EINVAL, "%s: empty tensor", who);
-  if (int st = check_head_dim(D, false)) return st;
-  if (int st = check_gqa(Hq, Hkv)) return st;
-  const int64_t M = (int64_t)Sq * (Hq / Hkv);
-  if (M > kDecodeMaxRows)
-    return fail(LBFA_EINVAL, "%s: Sq * (Hq / Hkv) = %lld query rows per kv head, the limit is %d (longer queries belong on the dense operator)",
-                who, (long long)M, kDecodeMaxRows);
-  if (int st = check_capacity(who, capacity)) return st;
-  if (max_seqlen_k < 1 || max_seqlen_k > capacity)
-    return fail(LBFA_EINVAL, "%s: max_seqlen_k must be in [1, capacity], got %d (capacity %d)", who, max_seqlen_k, capacity);
-  if (num_splits < 0 || num_splits > 65535) return fail(LBFA_EINVAL, "%s: num_splits must be in [0, 65535] (0: chosen by lbfa_decode_num_splits), got %d", who, num_splits);
-  if (int st = check_dtype(dtype)) return st;
-  if (int st = check_qmax(who, "q_qmax", q_qmax)) return st;
-  if (!(sm_scale > 0.0)) return fail(LBFA_EINVAL, "%s: sm_scale must be positive", who);
-  if (int st = check_input16(who, "q", tq)) return st;
-  if (!aligned(to, 8, 4)) return fail(LBFA_EINVAL, "%s: o must be 8-byte aligned with strides that are multiples of 4 elements", who);
-  if (!aligned(k_codes, 16) || !aligned(v_cache, 16) || !aligned(km, 16) || !aligned(k_scale, 4) || !aligned(seqlens, 4) || !aligned(lse, 4))
-    return fail(LBFA_EINVAL, "%s: cache tensors and km must be 16-byte aligned, k_scale / seqlens / lse 4-byte aligned", who);
-  const int splits = num_splits ? num_splits : lbfa_decode_num_splits(B, Hkv, max_seqlen_k);
-  const size_t need = lbfa_decode_workspace_bytes(B, Hq, Hkv, Sq, D, max_seqlen_k, splits);
-  if (need) {
-    if (int st = check_workspace(who, workspace, workspace_bytes, need)) return st;
-    if (!workspace) return fail(LBFA_EINVAL, "%s: null pointer", who);
-  }
-  if (B > 65535 || Hkv > 65535) return fail(LBFA_EINVAL, "%s: grid too large", who);
+  DecodeCall c = decode_call("lbfa_decode", q, dtype, k_codes, k_scale, v_cache, km, seqlens, o, lse, workspace, workspace_bytes, B,
+                             Hq, Hkv, Sq, D, max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax, is_causal,
+                             Pool{false, capacity, {}});
+  if (int st = check_decode(c)) return st;
   lbfa::DecodeParams p{};
-  p.q = (const unsigned short*)q; p.k_codes = k_codes; p.k_scale = k_scale; p.v = (const unsigned short*)v_cache;
-  p.km = lse ? (const unsigned short*)km : nullptr;  // km only enters the LSE correction
-  p.seqlens = seqlens; p.o = o; p.lse = lse;
-  p.qb = tq.st[0]; p.qh = tq.st[1]; p.qs = tq.st[2];
-  p.ob = to.st[0]; p.oh = to.st[1]; p.os = to.st[2];
-  p.B = B; p.Hq = Hq; p.Hkv = Hkv; p.Sq = Sq; p.group = Hq / Hkv; p.M = (int)M;
-  p.cap = capacity; p.max_k = max_seqlen_k; p.splits = splits; p.causal = is_causal ? 1 : 0;
-  p.q_sm_scale = (float)(sm_scale * 1.44269504);  // ONE rounding of the double product, as lbfa_forward
-  p.q_qmax = (float)q_qmax;
-  p.corr_scale = (float)sm_scale;
-  if (splits > 1) {
-    const size_t rows = (size_t)B * Hkv * splits * (size_t)M;
-    p.ws_acc = (float*)workspace;
-    p.ws_ml = (float*)((char*)workspace + align256(rows * D * sizeof(float)));
-  }
+  fill_decode(p, c);
   g_err[0] = 0;
   return check_hip(lbfa::launch_attn_decode(p, dtype, D, (hipStream_t)stream), "lbfa_decode launch");
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// the same two calls over a pool of pages behind a block table (kvcache_paged.hip, attn_paged_decode.hip)
-// ---------------------------------------------------------------------------------------------------------------
-namespace {
-// 0, or the refusal; on success *cap = max_pages_per_seq * page_size, the most keys a sequence can hold
-int check_pool(const char* who, int B, int num_slots, int num_pages, int page_size, int max_pages_per_seq, int* cap) {
-  if (page_size <= 0 || page_size % LBFA_BLKK != 0)
-    return fail(LBFA_EINVAL, "%s: page_size must be a positive multiple of 64, got %d", who, page_size);
-  if (num_pages < 1 || num_slots < 1 || max_pages_per_seq < 1)
-    return fail(LBFA_EINVAL, "%s: num_pages, num_slots and max_pages_per_seq must be at least 1, got %d, %d and %d", who, num_pages,
-                num_slots, max_pages_per_seq);
-  if ((int64_t)max_pages_per_seq * page_size > 0x7fffffffLL)
-    return fail(LBFA_EINVAL, "%s: max_pages_per_seq * page_size must stay below 2^31 keys", who);
-  if (B > num_slots) return fail(LBFA_EINVAL, "%s: B (%d) exceeds num_slots (%d)", who, B, num_slots);
-  *cap = max_pages_per_seq * page_size;
-  return 0;
-}
-}  // namespace
-
-int lbfa_kvcache_paged_append(const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
-                              int8_t* k_codes, float* k_scale, void* v_cache, void* k_tail, const int32_t* seqlens,
-                              const int32_t* block_table, const int32_t* slots, int B, int Hkv, int T, int D, int num_slots,
-                              int num_pages, int page_size, int max_pages_per_seq, const int64_t strides_k[3],
-                              const int64_t strides_v[3], int k_qmax, void* stream) {
-  const char* who = "lbfa_kvcache_paged_append";
-  const Operand tk = dense(k_new, strides_k), tv = dense(v_new, strides_v);
-  if (!tk.p || !tv.p || !k_codes || !k_scale || !v_cache || !k_tail || !seqlens || !block_table) return fail(LBFA_EINVAL, "%s: null pointer", who);
-  if (B <= 0 || Hkv <= 0 || T <= 0) return fail(LBFA_EINVAL, "%s: empty tensor", who);
-  if (int st = check_head_dim(D, false)) return st;
-  int cap = 0;
-  if (int st = check_pool(who, B, num_slots, num_pages, page_size, max_pages_per_seq, &cap)) return st;
-  if (int st = check_dtype(dtype)) return st;
-  if (int st = check_qmax(who, "k_qmax", k_qmax)) return st;
-  if (int st = check_input16(who, "k_new", tk)) return st;
-  if (int st = check_input16(who, "v_new", tv)) return st;
-  if (!aligned(k_codes, 16) || !aligned(v_cache, 16) || !aligned(k_tail, 16) || !aligned(km, 16) || !aligned(k_scale, 4) ||
-      !aligned(seqlens, 4) || !aligned(new_lens, 4) || !aligned(block_table, 4) || !aligned(slots, 4))
-    return fail(LBFA_EINVAL, "%s: cache tensors and km must be 16-byte aligned, k_scale / seqlens / new_lens / block_table / slots 4-byte aligned", who);
-  if (B > 65535 || Hkv > 65535) return fail(LBFA_EINVAL, "%s: grid too large", who);
-  lbfa::PagedAppendParams p{};
-  p.k_new = (const unsigned short*)k_new; p.v_new = (const unsigned short*)v_new;
-  p.new_lens = new_lens; p.km = (const unsigned short*)km;
-  p.k_codes = k_codes; p.k_scale = k_scale; p.v = (unsigned short*)v_cache; p.k_tail = (unsigned short*)k_tail;
-  p.seqlens = seqlens;
-  p.kb = tk.st[0]; p.kh = tk.st[1]; p.ks = tk.st[2];
-  p.vb = tv.st[0]; p.vh = tv.st[1]; p.vs = tv.st[2];
-  p.B = B; p.Hkv = Hkv; p.T = T; p.cap = cap;
-  p.qmax = (float)k_qmax;
-  p.block_table = block_table; p.slots = slots;
-  p.num_slots = num_slots; p.num_pages = num_pages; p.page_size = page_size; p.max_pages = max_pages_per_seq;
-  g_err[0] = 0;
-  return check_hip(lbfa::launch_kvcache_paged_append(p, dtype, D, (hipStream_t)stream), "lbfa_kvcache_paged_append launch");
 }
 
 int lbfa_decode_paged(const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const void* v_cache, const void* km,
@@ -1119,54 +1182,16 @@ int lbfa_decode_paged(const void* q, int dtype, const int8_t* k_codes, const flo
                       void* workspace, size_t workspace_bytes, int B, int Hq, int Hkv, int Sq, int D, int num_slots, int num_pages,
                       int page_size, int max_pages_per_seq, int max_seqlen_k, int num_splits, const int64_t strides_q[3],
                       const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream) {
-  const char* who = "lbfa_decode_paged";
-  const Operand tq = dense(q, strides_q), to = dense(o, strides_o);
-  if (!tq.p || !to.p || !k_codes || !k_scale || !v_cache || !seqlens || !block_table) return fail(LBFA_EINVAL, "%s: null pointer", who);
-  if (B <= 0 || Hq <= 0 || Hkv <= 0 || Sq <= 0) return fail(LBFA_EINVAL, "%s: empty tensor", who);
-  if (int st = check_head_dim(D, false)) return st;
-  if (int st = check_gqa(Hq, Hkv)) return st;
-  const int64_t M = (int64_t)Sq * (Hq / Hkv);
-  if (M > kDecodeMaxRows)
-    return fail(LBFA_EINVAL, "%s: Sq * (Hq / Hkv) = %lld query rows per kv head, the limit is %d (longer queries belong on the dense operator)",
-                who, (long long)M, kDecodeMaxRows);
-  int cap = 0;
-  if (int st = check_pool(who, B, num_slots, num_pages, page_size, max_pages_per_seq, &cap)) return st;
-  if (max_seqlen_k < 1 || max_seqlen_k > cap)
-    return fail(LBFA_EINVAL, "%s: max_seqlen_k must be in [1, max_pages_per_seq * page_size], got %d (limit %d)", who, max_seqlen_k, cap);
-  if (num_splits < 0 || num_splits > 65535) return fail(LBFA_EINVAL, "%s: num_splits must be in [0, 65535] (0: chosen by lbfa_decode_num_splits), got %d", who, num_splits);
-  if (int st = check_dtype(dtype)) return st;
-  if (int st = check_qmax(who, "q_qmax", q_qmax)) return st;
-  if (!(sm_scale > 0.0)) return fail(LBFA_EINVAL, "%s: sm_scale must be positive", who);
-  if (int st = check_input16(who, "q", tq)) return st;
-  if (!aligned(to, 8, 4)) return fail(LBFA_EINVAL, "%s: o must be 8-byte aligned with strides that are multiples of 4 elements", who);
-  if (!aligned(k_codes, 16) || !aligned(v_cache, 16) || !aligned(km, 16) || !aligned(k_scale, 4) || !aligned(seqlens, 4) ||
-      !aligned(block_table, 4) || !aligned(slots, 4) || !aligned(lse, 4))
-    return fail(LBFA_EINVAL, "%s: cache tensors and km must be 16-byte aligned, k_scale / seqlens / block_table / slots / lse 4-byte aligned", who);
-  const int splits = num_splits ? num_splits : lbfa_decode_num_splits(B, Hkv, max_seqlen_k);
-  const size_t need = lbfa_decode_workspace_bytes(B, Hq, Hkv, Sq, D, max_seqlen_k, splits);
-  if (need) {
-    if (int st = check_workspace(who, workspace, workspace_bytes, need)) return st;
-    if (!workspace) return fail(LBFA_EINVAL, "%s: null pointer", who);
-  }
-  if (B > 65535 || Hkv > 65535) return fail(LBFA_EINVAL, "%s: grid too large", who);
+  lbfa::PoolParams at{};
+  at.block_table = block_table; at.slots = slots;
+  at.num_slots = num_slots; at.num_pages = num_pages; at.page_size = page_size; at.max_pages = max_pages_per_seq;
+  DecodeCall c = decode_call("lbfa_decode_paged", q, dtype, k_codes, k_scale, v_cache, km, seqlens, o, lse, workspace,
+                             workspace_bytes, B, Hq, Hkv, Sq, D, max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax,
+                             is_causal, Pool{true, 0, at});
+  if (int st = check_decode(c)) return st;
   lbfa::PagedDecodeParams p{};
-  p.q = (const unsigned short*)q; p.k_codes = k_codes; p.k_scale = k_scale; p.v = (const unsigned short*)v_cache;
-  p.km = lse ? (const unsigned short*)km : nullptr;  // km only enters the LSE correction
-  p.seqlens = seqlens; p.o = o; p.lse = lse;
-  p.qb = tq.st[0]; p.qh = tq.st[1]; p.qs = tq.st[2];
-  p.ob = to.st[0]; p.oh = to.st[1]; p.os = to.st[2];
-  p.B = B; p.Hq = Hq; p.Hkv = Hkv; p.Sq = Sq; p.group = Hq / Hkv; p.M = (int)M;
-  p.cap = cap; p.max_k = max_seqlen_k; p.splits = splits; p.causal = is_causal ? 1 : 0;
-  p.q_sm_scale = (float)(sm_scale * 1.44269504);  // ONE rounding of the double product, as lbfa_decode
-  p.q_qmax = (float)q_qmax;
-  p.corr_scale = (float)sm_scale;
-  if (splits > 1) {
-    const size_t rows = (size_t)B * Hkv * splits * (size_t)M;
-    p.ws_acc = (float*)workspace;
-    p.ws_ml = (float*)((char*)workspace + align256(rows * D * sizeof(float)));
-  }
-  p.block_table = block_table; p.slots = slots;
-  p.num_slots = num_slots; p.num_pages = num_pages; p.page_size = page_size; p.max_pages = max_pages_per_seq;
+  fill_decode(p, c);
+  static_cast<lbfa::PoolParams&>(p) = c.pool.at;
   g_err[0] = 0;
   return check_hip(lbfa::launch_attn_paged_decode(p, dtype, D, (hipStream_t)stream), "lbfa_decode_paged launch");
 }

@@ -299,18 +299,15 @@ struct DecodeParams {
   float q_sm_scale, q_qmax, corr_scale;
 };
 
-// Paged cache (attn_paged_decode.hip, kvcache_paged.hip): a pool of pages [num_pages, Hkv, page_size, D] behind one block table per
-// sequence slot.  Key j of slot s lives in page block_table[s * max_pages + j / page_size], row j % page_size.  Row b of a call
-// addresses slot slots[b] (null: slot b).  The fields extend the contiguous structs, whose kernels never see them.
-struct PagedDecodeParams : DecodeParams {
+// Paged cache: a pool of pages [num_pages, Hkv, page_size, D] behind one block table per sequence slot.  Key j of slot s lives in
+// page block_table[s * max_pages + j / page_size], row j % page_size.  Row b of a call addresses slot slots[b] (null: slot b).
+// The fields extend the contiguous structs; only the paged instances of the kernels (attn_decode.hip, kvcache.hip) see them.
+struct PoolParams {
   const int* block_table;  // [num_slots, max_pages]
   const int* slots;        // [B] or null
   int num_slots, num_pages, page_size, max_pages;
 };
-struct PagedAppendParams : AppendParams {  // cap = max_pages * page_size
-  const int* block_table;
-  const int* slots;
-  int num_slots, num_pages, page_size, max_pages;
-};
+struct PagedDecodeParams : DecodeParams, PoolParams {};
+struct PagedAppendParams : AppendParams, PoolParams {};  // cap = max_pages * page_size
 
 }  // namespace lbfa

@@ -27,6 +27,55 @@ def _padded_head_dim(d: int) -> int:
     return 64 if d <= 64 else 128
 
 
+def _append_operands(cache, k, v, tensor_layout: str):
+    """The checks both caches make of the rows offered to `append`: -> ops, k, v (head dim zero-padded, last stride 1),
+    (rows, heads, T) and the {batch, head, seq} strides of k and of v"""
+    ops = ops_for(k)
+    if tensor_layout not in ("HND", "NHD"):
+        raise ValueError(f"Unknown tensor layout: {tensor_layout}")
+    if k.dtype != cache.dtype or v.dtype != cache.dtype:
+        raise ValueError("k and v must have the dtype of the cache")
+    if k.device != cache.device or v.device != cache.device:
+        raise ValueError("k and v must be on the device of the cache")
+    if tuple(k.shape) != tuple(v.shape) or k.dim() != 4:
+        raise ValueError("k and v must be 4-D tensors of the same shape")
+    pad = cache.padded_head_dim - cache.head_dim
+    if k.shape[-1] != cache.head_dim:
+        raise ValueError(f"head_dim {k.shape[-1]} does not match the cache ({cache.head_dim})")
+    if pad:  # only the new tokens are padded
+        k, v = ops.pad_last(k, pad), ops.pad_last(v, pad)
+    if k.stride(-1) != 1:
+        k = k.contiguous()
+    if v.stride(-1) != 1:
+        v = v.contiguous()
+    bht, k3 = _qpb._bhs(ops.shape(k), ops.strides(k), tensor_layout)
+    _, v3 = _qpb._bhs(ops.shape(v), ops.strides(v), tensor_layout)
+    return ops, k, v, bht, k3, v3
+
+
+def _new_lens_i32(cache, ops, new_lens, n: int, per: str):
+    """new_lens of an append of n rows as an int32 tensor on the cache's device (None stays None)"""
+    if new_lens is not None:
+        new_lens = new_lens.to(device=cache.device, dtype=ops.torch.int32).contiguous()
+        if tuple(new_lens.shape) != (n,):
+            raise ValueError(f"new_lens must have one entry per {per}")
+    return new_lens
+
+
+def _first_append_mean(lib, ops, k, k3, new_lens, km, B: int, H: int, T: int, D: int, stream):
+    """smooth-K mean of the rows of a first append into km [B, H, D]: lbfa_mean_seq, the mean of the dense operators (the codes
+    of a prefill are theirs), or lbfa_kvcache_mean over the first new_lens[b] rows of a ragged one"""
+    code = ops.dtype_code(k)
+    if new_lens is None:
+        ws_bytes = lib.lbfa_mean_seq_workspace_bytes(B, H, T, D)
+        ws = ops.torch.empty((max(ws_bytes, 16),), dtype=ops.torch.uint8, device=k.device)
+        _lib.check(lib.lbfa_mean_seq(k.data_ptr(), code, km.data_ptr(), ws.data_ptr(), ws_bytes, B, H, T, D, _lib.strides3(k3),
+                                     stream), lib)
+    else:
+        _lib.check(lib.lbfa_kvcache_mean(k.data_ptr(), code, new_lens.data_ptr(), km.data_ptr(), B, H, T, D, _lib.strides3(k3),
+                                         stream), lib)
+
+
 class LowbitKVCache:
     """Pre-allocated cache of `batch` sequences of up to `capacity` keys (rounded up to a multiple of 64).
 
@@ -65,50 +114,21 @@ class LowbitKVCache:
     def append(self, k, v, tensor_layout: str = "HND", new_lens=None):
         """Append k, v [B, Hkv, T, D] ("HND") or [B, T, Hkv, D] ("NHD"); sequence b takes the first new_lens[b] rows (an int32
         device tensor [B], None: all T).  Returns self."""
-        ops = ops_for(k)
+        ops, k, v, (B, H, T), k3, v3 = _append_operands(self, k, v, tensor_layout)
         torch = ops.torch
-        if tensor_layout not in ("HND", "NHD"):
-            raise ValueError(f"Unknown tensor layout: {tensor_layout}")
-        if k.dtype != self.dtype or v.dtype != self.dtype:
-            raise ValueError("k and v must have the dtype of the cache")
-        if k.device != self.device or v.device != self.device:
-            raise ValueError("k and v must be on the device of the cache")
-        if tuple(k.shape) != tuple(v.shape) or k.dim() != 4:
-            raise ValueError("k and v must be 4-D tensors of the same shape")
-        pad = self.padded_head_dim - self.head_dim
-        if k.shape[-1] != self.head_dim:
-            raise ValueError(f"head_dim {k.shape[-1]} does not match the cache ({self.head_dim})")
-        if pad:  # only the new tokens are padded
-            k, v = ops.pad_last(k, pad), ops.pad_last(v, pad)
-        if k.stride(-1) != 1:
-            k = k.contiguous()
-        if v.stride(-1) != 1:
-            v = v.contiguous()
-        (B, H, T), k3 = _qpb._bhs(ops.shape(k), ops.strides(k), tensor_layout)
-        (_, _, _), v3 = _qpb._bhs(ops.shape(v), ops.strides(v), tensor_layout)
         if B != self.batch or H != self.num_kv_heads:
             raise ValueError(f"expected batch {self.batch} and {self.num_kv_heads} kv heads, got {B} and {H}")
         if T == 0:
             return self
         if self.max_seqlen + T > self.capacity:
             raise ValueError(f"appending {T} tokens to at most {self.max_seqlen} would pass the capacity {self.capacity}")
-        if new_lens is not None:
-            new_lens = new_lens.to(device=self.device, dtype=torch.int32).contiguous()
-            if tuple(new_lens.shape) != (self.batch,):
-                raise ValueError("new_lens must have one entry per sequence")
+        new_lens = _new_lens_i32(self, ops, new_lens, self.batch, "sequence")
         lib = _lib.load()
         D, code = self.padded_head_dim, ops.dtype_code(k)
         with ops.device_guard(k):
             stream = ops.stream(k)
             if self.smooth_k and not self._has_km:
-                if new_lens is None:  # the mean of the dense operators: the codes of a prefill are theirs
-                    ws_bytes = lib.lbfa_mean_seq_workspace_bytes(B, H, T, D)
-                    ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=self.device)
-                    _lib.check(lib.lbfa_mean_seq(k.data_ptr(), code, self.km.data_ptr(), ws.data_ptr(), ws_bytes, B, H, T, D,
-                                                 _lib.strides3(k3), stream), lib)
-                else:
-                    _lib.check(lib.lbfa_kvcache_mean(k.data_ptr(), code, new_lens.data_ptr(), self.km.data_ptr(), B, H, T, D,
-                                                     _lib.strides3(k3), stream), lib)
+                _first_append_mean(lib, ops, k, k3, new_lens, self.km, B, H, T, D, stream)
                 self._has_km = True
             _lib.check(lib.lbfa_kvcache_append(k.data_ptr(), v.data_ptr(), code, new_lens.data_ptr() if new_lens is not None else None,
                                                self.km.data_ptr() if self.smooth_k else None, self.k_codes.data_ptr(),
@@ -253,35 +273,13 @@ class LowbitPagedKVCache:
         max_pages_per_seq * page_size) leave the cache as it was.  Returns self."""
         slots_given = slots is not None
         slots = _slot_list(slots, int(k.shape[0]), self.max_seqs)
-        ops = ops_for(k)
+        ops, k, v, (n, H, T), k3, v3 = _append_operands(self, k, v, tensor_layout)
         torch = ops.torch
-        if tensor_layout not in ("HND", "NHD"):
-            raise ValueError(f"Unknown tensor layout: {tensor_layout}")
-        if k.dtype != self.dtype or v.dtype != self.dtype:
-            raise ValueError("k and v must have the dtype of the cache")
-        if k.device != self.device or v.device != self.device:
-            raise ValueError("k and v must be on the device of the cache")
-        if tuple(k.shape) != tuple(v.shape) or k.dim() != 4:
-            raise ValueError("k and v must be 4-D tensors of the same shape")
-        pad = self.padded_head_dim - self.head_dim
-        if k.shape[-1] != self.head_dim:
-            raise ValueError(f"head_dim {k.shape[-1]} does not match the cache ({self.head_dim})")
-        if pad:  # only the new tokens are padded
-            k, v = ops.pad_last(k, pad), ops.pad_last(v, pad)
-        if k.stride(-1) != 1:
-            k = k.contiguous()
-        if v.stride(-1) != 1:
-            v = v.contiguous()
-        (n, H, T), k3 = _qpb._bhs(ops.shape(k), ops.strides(k), tensor_layout)
-        (_, _, _), v3 = _qpb._bhs(ops.shape(v), ops.strides(v), tensor_layout)
         if H != self.num_kv_heads:
             raise ValueError(f"expected {self.num_kv_heads} kv heads, got {H}")
         if T == 0:
             return self
-        if new_lens is not None:
-            new_lens = new_lens.to(device=self.device, dtype=torch.int32).contiguous()
-            if tuple(new_lens.shape) != (n,):
-                raise ValueError("new_lens must have one entry per row")
+        new_lens = _new_lens_i32(self, ops, new_lens, n, "row")
         fresh = [i for i, s in enumerate(slots) if self.allocator.bound[s] == 0]  # rows whose sequence starts here
         changed = self.allocator.reserve(slots, T)  # raises with nothing changed
         lib = _lib.load()
@@ -295,14 +293,7 @@ class LowbitPagedKVCache:
             slot_t = torch.tensor(slots, dtype=torch.int32, device=self.device) if slots_given else None
             if self.smooth_k and fresh:
                 km_new = torch.empty((n, H, D), dtype=self.dtype, device=self.device)
-                if new_lens is None:  # the mean of the dense operators: the codes of a prefill are theirs
-                    ws_bytes = lib.lbfa_mean_seq_workspace_bytes(n, H, T, D)
-                    ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=self.device)
-                    _lib.check(lib.lbfa_mean_seq(k.data_ptr(), code, km_new.data_ptr(), ws.data_ptr(), ws_bytes, n, H, T, D,
-                                                 _lib.strides3(k3), stream), lib)
-                else:
-                    _lib.check(lib.lbfa_kvcache_mean(k.data_ptr(), code, new_lens.data_ptr(), km_new.data_ptr(), n, H, T, D,
-                                                     _lib.strides3(k3), stream), lib)
+                _first_append_mean(lib, ops, k, k3, new_lens, km_new, n, H, T, D, stream)
                 rows = torch.tensor(fresh, dtype=torch.int64, device=self.device)
                 self.km.index_copy_(0, torch.tensor([slots[i] for i in fresh], dtype=torch.int64, device=self.device), km_new[rows])
             _lib.check(lib.lbfa_kvcache_paged_append(
@@ -403,25 +394,22 @@ def lowbit_fa_decode(q, cache, tensor_layout: str = "HND", is_causal: bool = Fal
     max_k = max(1, min(cache.max_seqlen(slot_list), cache.allocator.capacity) if paged else min(cache.max_seqlen, cache.capacity))
     ws_bytes = lib.lbfa_decode_workspace_bytes(B, Hq, Hkv, Sq, D, max_k, int(num_splits))
     ws = ops.empty((max(ws_bytes, 16),), ops.uint8, q)
-    if paged:
-        with ops.device_guard(q):
-            slot_t = torch.tensor(slot_list, dtype=torch.int32, device=cache.device) if slots is not None else None
-            _lib.check(lib.lbfa_decode_paged(
-                q.data_ptr(), ops.dtype_code(q), cache.k_codes.data_ptr(), cache.k_scale.data_ptr(), cache.v.data_ptr(),
-                cache.km.data_ptr() if cache.km is not None else None, cache.seqlens.data_ptr(), cache.block_table.data_ptr(),
-                slot_t.data_ptr() if slot_t is not None else None, o.data_ptr(), lse.data_ptr() if return_lse else None,
-                ws.data_ptr(), ws_bytes, B, Hq, Hkv, Sq, D, cache.max_seqs, cache.num_pages, cache.page_size,
-                cache.max_pages_per_seq, max_k, int(num_splits), _lib.strides3(q3), _lib.strides3(o3), float(sm_scale),
-                127 if q_bits == 8 else 7, 1 if is_causal else 0, ops.stream(q)), lib)
-        o = o[..., :head_dim_og]
-        return (o, lse) if return_lse else o
     with ops.device_guard(q):
-        _lib.check(lib.lbfa_decode(q.data_ptr(), ops.dtype_code(q), cache.k_codes.data_ptr(), cache.k_scale.data_ptr(),
-                                   cache.v.data_ptr(), cache.km.data_ptr() if cache.km is not None else None,
-                                   cache.seqlens.data_ptr(), o.data_ptr(), lse.data_ptr() if return_lse else None,
-                                   ws.data_ptr(), ws_bytes, B, Hq, Hkv, Sq, D, cache.capacity, max_k, int(num_splits),
-                                   _lib.strides3(q3), _lib.strides3(o3), float(sm_scale), 127 if q_bits == 8 else 7,
-                                   1 if is_causal else 0, ops.stream(q)), lib)
+        # The arguments the two entry points share, in the order of include/lowbit_fa.h:
+        #   lbfa_decode:        head (q .. seqlens), out (o .. D), capacity, rest (max_seqlen_k .. stream)
+        #   lbfa_decode_paged:  head, block_table, slots, out, num_slots .. max_pages_per_seq, rest
+        head = (q.data_ptr(), ops.dtype_code(q), cache.k_codes.data_ptr(), cache.k_scale.data_ptr(), cache.v.data_ptr(),
+                cache.km.data_ptr() if cache.km is not None else None, cache.seqlens.data_ptr())
+        out = (o.data_ptr(), lse.data_ptr() if return_lse else None, ws.data_ptr(), ws_bytes, B, Hq, Hkv, Sq, D)
+        rest = (max_k, int(num_splits), _lib.strides3(q3), _lib.strides3(o3), float(sm_scale), 127 if q_bits == 8 else 7,
+                1 if is_causal else 0, ops.stream(q))
+        if paged:
+            slot_t = torch.tensor(slot_list, dtype=torch.int32, device=cache.device) if slots is not None else None
+            status = lib.lbfa_decode_paged(*head, cache.block_table.data_ptr(), slot_t.data_ptr() if slot_t is not None else None,
+                                           *out, cache.max_seqs, cache.num_pages, cache.page_size, cache.max_pages_per_seq, *rest)
+        else:
+            status = lib.lbfa_decode(*head, *out, cache.capacity, *rest)
+        _lib.check(status, lib)
     o = o[..., :head_dim_og]
     return (o, lse) if return_lse else o
 

@@ -499,7 +499,7 @@ def test_paged_append_skips_corrupt_ids(monkeypatch, dev, dtype, D, page):
 @pytest.mark.parametrize("dtype,D,page,ns", [("fp16", 64, 64, 1), ("bf16", 128, 128, 3)])
 def test_paged_decode_clamps_corrupt_ids(monkeypatch, dev, dtype, D, page, ns):
     """lbfa_decode_paged (C ABI) with slots [-1, 1, num_slots] and the pages -1 and num_pages + 1 in the middle of slot 1's
-    table.  attn_paged_decode.hip clamps a slot into [0, num_slots - 1] and a page into [0, num_pages - 1]
+    table.  attn_decode.hip's PagedKV clamps a slot into [0, num_slots - 1] and a page into [0, num_pages - 1]
     (`min(max(id, 0), n - 1)`): the expected result is the same call with slots [0, 1, num_slots - 1] and the pages 0 and
     num_pages - 1 in those entries, bit for bit, and it is finite - every page of the pool holds finite data here.
 
