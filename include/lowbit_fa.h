@@ -367,7 +367,7 @@ int lbfa_kvcache_append(const void* k_new, const void* v_new, int dtype, const i
 
 /*
  * lbfa_decode: O = softmax(dequant(Q K^T)) V of q [B, Hq, Sq, D] (fp16 / bf16, strides_q) over the cache, for
- * M = Sq * (Hq / Hkv) <= 64 query rows per kv head (more: LBFA_EINVAL - such calls belong on the dense operator).
+ * M = Sq * (Hq / Hkv) <= 64 query rows per kv head (more: LBFA_EINVAL - such calls belong on lbfa_prefill below; the message names the dense operator).
  *   seqlens[b]    : valid keys of sequence b, the tokens just appended included; max_seqlen_k (1 .. capacity) is a host upper
  *                   bound that sizes the grid, longer sequences are cut there.  seqlens[b] == 0: zeros and LSE -inf.
  *   Q             : quantised inside the kernel, the Sq rows of one (batch, head) as one block with fp32(sm_scale * 1.44269504)
@@ -435,6 +435,57 @@ int lbfa_decode_paged(const void* q, int dtype, const int8_t* k_codes, const flo
                       void* workspace, size_t workspace_bytes, int B, int Hq, int Hkv, int Sq, int D, int num_slots, int num_pages,
                       int page_size, int max_pages_per_seq, int max_seqlen_k, int num_splits, const int64_t strides_q[3],
                       const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream);
+
+/*
+ * Cached prefill: attention of ANY number of queries to the same caches (additive to ABI 200, LBFA_VERSION unchanged: look the
+ * symbols up).  lbfa_decode keeps refusing Sq * (Hq / Hkv) > 64; calls at or below that limit belong there.
+ *
+ * lbfa_prefill: O = softmax(dequant(Q K^T)) V of q [B, Hq, Sq, D] (fp16 / bf16, strides_q) over the contiguous cache, Sq >= 1.
+ *   keys          : seqlens[b] valid keys of sequence b, the keys of these queries appended first; max_seqlen_k (1 .. capacity) is
+ *                   the host upper bound, longer sequences are cut there.  Keys >= seqlens[b] are masked with -inf and their V
+ *                   rows enter as zeros (stale cache rows may hold anything).
+ *   q_lens        : int32 [B] on the device, or NULL (all Sq): sequence b owns the first q_lens[b] rows of q[b], the value
+ *                   clamped to [0, Sq] on the device.  Rows at or past it are written as zeros with LSE -inf.  The result for
+ *                   sequence b equals the call on q[b, :, :q_lens[b]] alone.  The counterpart of new_lens of the append.
+ *   Q             : quantised inside the kernel in blocks of 128 rows counted from row 0 of each (batch, query head), the last
+ *                   block cut at q_lens[b], its amax taken over its valid rows, with fp32(sm_scale * 1.44269504) formed in
+ *                   double: codes and scales bit-identical to lbfa_quant_per_block (blk = 128) on the valid rows; q_qmax in
+ *                   {127, 7}.  A cache filled by one uniform append and read with Sq == Sk sees exactly the Q and K codes of
+ *                   the dense operator.
+ *   arithmetic    : the decode kernel's - scores fp32(int32(q . k)) * q_scale * k_scale, online softmax in base 2 on the exact
+ *                   argument s - m, P rounded to fp16, fp16 MFMA against v_cache, fp32 accumulation.
+ *   is_causal     : bottom-right aligned - query i of sequence b sees keys < seqlens[b] - q_lens[b] + 1 + i (a query that sees
+ *                   none: zeros, -inf).  A Q block skips every 64-key tile wholly past its last row's limit.
+ *   lse           : NULL or [B, Hq, Sq] fp32 natural log, including dtype(q . km) * sm_scale as lbfa_decode defines it.
+ *   num_splits    : key slices, cut at multiples of 64 keys over the tiles a Q block can see (slice s = tiles [s * tps,
+ *                   (s + 1) * tps) of them, tps = ceil(tiles / num_splits)); 0 = lbfa_prefill_num_splits(B, Hq, Sq, max_seqlen_k):
+ *                   max(1, min(ceil(512 / (B * Hq * ceil(Sq / 128))), tiles / 4, 256)), tiles = ceil(max_seqlen_k / 64).  One
+ *                   slice writes o and lse directly; more write the decode kernel's fp32 partials ([B, Hkv, splits, M, D] and
+ *                   [.., M, 4], row hl * Sq + sq, M = Sq * (Hq / Hkv)) and the decode call's second kernel adds them in one
+ *                   fixed order: no atomics, bitwise reproducible for a given num_splits.
+ *   workspace     : >= lbfa_prefill_workspace_bytes(..., num_splits) bytes, 16-byte aligned (0 bytes / NULL with one slice).
+ *   All offsets are 64-bit: no 2 GiB window.  Every host-visible argument is checked before the first launch: LBFA_EINVAL means
+ *   nothing was enqueued.
+ *   Grid limits (LBFA_EINVAL "grid too large"): B, Hq, Hkv <= 65535; Sq * (Hq / Hkv) and ceil(Sq / 128) * num_splits < 2^24.
+ * lbfa_prefill_paged: the same over the pool of pages, with the arguments and the device-side defences of lbfa_decode_paged
+ * (slot and page ids are clamped into range: a corrupt table gives a wrong answer, never an address outside the pool; the pool
+ * may exceed 4 GiB).  q_lens is indexed by row of the call, seqlens / km / block_table by slot.  Same O and LSE as lbfa_prefill
+ * bit for bit for the same num_splits.
+ * Not built: a backward through the cache, fp8 PV over the cache, prefix sharing / copy-on-write, Paddle tensors, routing
+ * lbfa_decode calls with more than 64 rows here.
+ */
+int lbfa_prefill_num_splits(int B, int Hq, int Sq, int max_seqlen_k);
+size_t lbfa_prefill_workspace_bytes(int B, int Hq, int Hkv, int Sq, int D, int max_seqlen_k, int num_splits);
+int lbfa_prefill(const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const void* v_cache, const void* km,
+                 const int32_t* seqlens, const int32_t* q_lens, void* o, float* lse, void* workspace, size_t workspace_bytes,
+                 int B, int Hq, int Hkv, int Sq, int D, int capacity, int max_seqlen_k, int num_splits,
+                 const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream);
+int lbfa_prefill_paged(const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const void* v_cache, const void* km,
+                       const int32_t* seqlens, const int32_t* q_lens, const int32_t* block_table, const int32_t* slots, void* o,
+                       float* lse, void* workspace, size_t workspace_bytes, int B, int Hq, int Hkv, int Sq, int D, int num_slots,
+                       int num_pages, int page_size, int max_pages_per_seq, int max_seqlen_k, int num_splits,
+                       const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal,
+                       void* stream);
 
 #ifdef __cplusplus
 }

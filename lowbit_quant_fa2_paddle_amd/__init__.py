@@ -27,6 +27,9 @@ from .kvcache import (  # noqa: F401
     PageAllocator,
     lowbit_fa_decode,
     sageattn_decode,
+    # cached prefill: any number of queries over the same caches
+    lowbit_fa_prefill,
+    sageattn_prefill,
 )
 
 __version__ = "0.1.0"

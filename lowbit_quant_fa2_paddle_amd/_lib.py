@@ -86,6 +86,13 @@ SIGNATURES = {
                                         ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _ci, _vp]),
     "lbfa_decode_paged": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _ci, _ci, _ci, _ci, _ci, _ci, _ci,
                                 _ci, _ci, _ci, _ci, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _cd, _ci, _ci, _vp]),
+    "lbfa_prefill_num_splits": (_ci, [_ci, _ci, _ci, _ci]),
+    "lbfa_prefill_workspace_bytes": (_sz, [_ci] * 7),
+    "lbfa_prefill": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci,
+                           ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _cd, _ci, _ci, _vp]),
+    "lbfa_prefill_paged": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _ci, _ci, _ci, _ci, _ci, _ci,
+                                 _ci, _ci, _ci, _ci, _ci, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _cd, _ci, _ci,
+                                 _vp]),
 }
 
 _lock = threading.Lock()

@@ -29,6 +29,9 @@ hipError_t launch_kvcache_paged_append(const PagedAppendParams& p, int dtype, in
 hipError_t launch_kvcache_mean(const RaggedMeanParams& p, int dtype, int B, int D, hipStream_t stream);
 hipError_t launch_attn_decode(const DecodeParams& p, int dtype, int D, hipStream_t stream);
 hipError_t launch_attn_paged_decode(const PagedDecodeParams& p, int dtype, int D, hipStream_t stream);
+// defined in attn_prefill.hip
+hipError_t launch_attn_prefill(const PrefillParams& p, int dtype, int D, hipStream_t stream);
+hipError_t launch_attn_paged_prefill(const PagedPrefillParams& p, int dtype, int D, hipStream_t stream);
 }  // namespace lbfa
 
 namespace {
@@ -932,6 +935,8 @@ constexpr int kDecodeMaxRows = 64;     // query rows per kv head one decode work
 constexpr int kDecodeWaves = 1024;     // workgroups (one wave each) that fill the part: 256 CUs x 4 SIMDs
 constexpr int kDecodeMinTiles = 4;     // no key slice shorter than 4 tiles of 64 keys
 constexpr int kDecodeMaxSplits = 256;
+constexpr int64_t kPrefillMaxGridX = (1 << 24) - 1;  // x extent of the prefill and combine grids (256 threads each)
+constexpr int kPrefillGroups = 512;    // four-wave workgroups that fill the part: 256 CUs x 2
 
 // Where the keys live.  Contiguous: {false, capacity}.  Paged: {true, 0, the pool}; check_pool sets cap = max_pages * page_size.
 struct Pool {
@@ -1024,6 +1029,9 @@ struct DecodeCall {
   int q_qmax, is_causal;
   Pool pool;
   int splits;  // set by check_decode: num_splits, or the split rule's choice
+  // cached prefill (lbfa_prefill[_paged]): the same call for any Sq, with ragged query lengths
+  bool prefill;
+  const int32_t* q_lens;
 };
 DecodeCall decode_call(const char* who, const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const void* v_cache,
                        const void* km, const int32_t* seqlens, void* o, float* lse, void* workspace, size_t workspace_bytes, int B,
@@ -1045,7 +1053,7 @@ int check_decode(DecodeCall& c) {
   if (int st = check_head_dim(c.D, false)) return st;
   if (int st = check_gqa(c.Hq, c.Hkv)) return st;
   const int64_t M = (int64_t)c.Sq * (c.Hq / c.Hkv);
-  if (M > kDecodeMaxRows)
+  if (!c.prefill && M > kDecodeMaxRows)
     return fail(LBFA_EINVAL, "%s: Sq * (Hq / Hkv) = %lld query rows per kv head, the limit is %d (longer queries belong on the dense operator)",
                 who, (long long)M, kDecodeMaxRows);
   if (int st = check_pool(who, c.B, c.pool)) return st;
@@ -1053,17 +1061,25 @@ int check_decode(DecodeCall& c) {
     return c.pool.paged ? fail(LBFA_EINVAL, "%s: max_seqlen_k must be in [1, max_pages_per_seq * page_size], got %d (limit %d)", who,
                                c.max_seqlen_k, c.pool.cap)
                         : fail(LBFA_EINVAL, "%s: max_seqlen_k must be in [1, capacity], got %d (capacity %d)", who, c.max_seqlen_k, c.pool.cap);
-  if (c.num_splits < 0 || c.num_splits > 65535) return fail(LBFA_EINVAL, "%s: num_splits must be in [0, 65535] (0: chosen by lbfa_decode_num_splits), got %d", who, c.num_splits);
+  if (c.num_splits < 0 || c.num_splits > 65535)
+    return fail(LBFA_EINVAL, "%s: num_splits must be in [0, 65535] (0: chosen by %s), got %d", who,
+                c.prefill ? "lbfa_prefill_num_splits" : "lbfa_decode_num_splits", c.num_splits);
   if (int st = check_dtype(c.dtype)) return st;
   if (int st = check_qmax(who, "q_qmax", c.q_qmax)) return st;
   if (!(c.sm_scale > 0.0)) return fail(LBFA_EINVAL, "%s: sm_scale must be positive", who);
   if (int st = check_input16(who, "q", c.q)) return st;
   if (!aligned(c.o, 8, 4)) return fail(LBFA_EINVAL, "%s: o must be 8-byte aligned with strides that are multiples of 4 elements", who);
   if (!aligned(c.k_codes, 16) || !aligned(c.v_cache, 16) || !aligned(c.km, 16) || !aligned(c.k_scale, 4) || !aligned(c.seqlens, 4) ||
-      !pool_aligned(c.pool) || !aligned(c.lse, 4))
-    return fail(LBFA_EINVAL, "%s: cache tensors and km must be 16-byte aligned, k_scale / seqlens%s / lse 4-byte aligned", who,
-                c.pool.paged ? " / block_table / slots" : "");
-  c.splits = c.num_splits ? c.num_splits : lbfa_decode_num_splits(c.B, c.Hkv, c.max_seqlen_k);
+      !pool_aligned(c.pool) || !aligned(c.lse, 4) || !aligned(c.q_lens, 4))
+    return fail(LBFA_EINVAL, "%s: cache tensors and km must be 16-byte aligned, k_scale / seqlens%s%s / lse 4-byte aligned", who,
+                c.prefill ? " / q_lens" : "", c.pool.paged ? " / block_table / slots" : "");
+  if (c.prefill) c.splits = c.num_splits ? c.num_splits : lbfa_prefill_num_splits(c.B, c.Hq, c.Sq, c.max_seqlen_k);
+  else c.splits = c.num_splits ? c.num_splits : lbfa_decode_num_splits(c.B, c.Hkv, c.max_seqlen_k);
+  // prefill: grid (Q blocks x slices, Hq, B) of 256 threads, the combine's (M, Hkv, B) of 256: a launch whose gridDim.x * blockDim.x
+  // reaches 2^32 is refused by the runtime, and the combine is the SECOND launch - so both are bounded here, before the first
+  if (c.prefill && (c.Hq > 65535 || M > kPrefillMaxGridX || ((int64_t)c.Sq + LBFA_BLKQ - 1) / LBFA_BLKQ * c.splits > kPrefillMaxGridX))
+    return fail(LBFA_EINVAL, "%s: grid too large (Sq * (Hq / Hkv) and ceil(Sq / 128) * num_splits must stay below 2^24, Hq below 65536)", who);
+  // (the partials of both operators have the same size: one row per query row and slice)
   if (const size_t need = lbfa_decode_workspace_bytes(c.B, c.Hq, c.Hkv, c.Sq, c.D, c.max_seqlen_k, c.splits)) {
     if (int st = check_workspace(who, c.workspace, c.workspace_bytes, need)) return st;
     if (!c.workspace) return fail(LBFA_EINVAL, "%s: null pointer", who);
@@ -1194,6 +1210,69 @@ int lbfa_decode_paged(const void* q, int dtype, const int8_t* k_codes, const flo
   static_cast<lbfa::PoolParams&>(p) = c.pool.at;
   g_err[0] = 0;
   return check_hip(lbfa::launch_attn_paged_decode(p, dtype, D, (hipStream_t)stream), "lbfa_decode_paged launch");
+}
+
+// The split rule of the cached prefill: as many key slices as it takes for B * Hq * ceil(Sq / 128) four-wave workgroups to reach
+// 512 (two per CU, the analogue of decode's four one-wave ones), no slice shorter than 4 tiles of 64 keys, at most 256.
+int lbfa_prefill_num_splits(int B, int Hq, int Sq, int max_seqlen_k) {
+  if (B <= 0 || Hq <= 0 || Sq <= 0 || max_seqlen_k <= 0) return 1;
+  const int64_t groups = (int64_t)B * Hq * (((int64_t)Sq + LBFA_BLKQ - 1) / LBFA_BLKQ);
+  const int64_t tiles = ((int64_t)max_seqlen_k + LBFA_BLKK - 1) / LBFA_BLKK;
+  int64_t s = (kPrefillGroups + groups - 1) / groups;
+  if (s > tiles / kDecodeMinTiles) s = tiles / kDecodeMinTiles;
+  if (s > kDecodeMaxSplits) s = kDecodeMaxSplits;
+  return s < 1 ? 1 : (int)s;
+}
+
+size_t lbfa_prefill_workspace_bytes(int B, int Hq, int Hkv, int Sq, int D, int max_seqlen_k, int num_splits) {
+  if (B <= 0 || Hq <= 0 || Hkv <= 0 || Sq <= 0 || num_splits < 0) return 0;
+  const int splits = num_splits ? num_splits : lbfa_prefill_num_splits(B, Hq, Sq, max_seqlen_k);
+  return lbfa_decode_workspace_bytes(B, Hq, Hkv, Sq, D, max_seqlen_k, splits);  // the decode kernel's partials
+}
+
+namespace {
+void fill_prefill(int& nQ, const int*& q_lens, const DecodeCall& c) {
+  nQ = (c.Sq + LBFA_BLKQ - 1) / LBFA_BLKQ;
+  q_lens = c.q_lens;
+}
+}  // namespace
+
+int lbfa_prefill(const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const void* v_cache, const void* km,
+                 const int32_t* seqlens, const int32_t* q_lens, void* o, float* lse, void* workspace, size_t workspace_bytes,
+                 int B, int Hq, int Hkv, int Sq, int D, int capacity, int max_seqlen_k, int num_splits,
+                 const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream) {
+  DecodeCall c = decode_call("lbfa_prefill", q, dtype, k_codes, k_scale, v_cache, km, seqlens, o, lse, workspace, workspace_bytes, B,
+                             Hq, Hkv, Sq, D, max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax, is_causal,
+                             Pool{false, capacity, {}});
+  c.prefill = true; c.q_lens = q_lens;
+  if (int st = check_decode(c)) return st;
+  lbfa::PrefillParams p{};
+  fill_decode(p, c);
+  fill_prefill(p.nQ, p.q_lens, c);
+  g_err[0] = 0;
+  return check_hip(lbfa::launch_attn_prefill(p, dtype, D, (hipStream_t)stream), "lbfa_prefill launch");
+}
+
+int lbfa_prefill_paged(const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const void* v_cache, const void* km,
+                       const int32_t* seqlens, const int32_t* q_lens, const int32_t* block_table, const int32_t* slots, void* o,
+                       float* lse, void* workspace, size_t workspace_bytes, int B, int Hq, int Hkv, int Sq, int D, int num_slots,
+                       int num_pages, int page_size, int max_pages_per_seq, int max_seqlen_k, int num_splits,
+                       const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal,
+                       void* stream) {
+  lbfa::PoolParams at{};
+  at.block_table = block_table; at.slots = slots;
+  at.num_slots = num_slots; at.num_pages = num_pages; at.page_size = page_size; at.max_pages = max_pages_per_seq;
+  DecodeCall c = decode_call("lbfa_prefill_paged", q, dtype, k_codes, k_scale, v_cache, km, seqlens, o, lse, workspace,
+                             workspace_bytes, B, Hq, Hkv, Sq, D, max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax,
+                             is_causal, Pool{true, 0, at});
+  c.prefill = true; c.q_lens = q_lens;
+  if (int st = check_decode(c)) return st;
+  lbfa::PagedPrefillParams p{};
+  fill_decode(p, c);
+  static_cast<lbfa::PoolParams&>(p) = c.pool.at;
+  fill_prefill(p.nQ, p.q_lens, c);
+  g_err[0] = 0;
+  return check_hip(lbfa::launch_attn_paged_prefill(p, dtype, D, (hipStream_t)stream), "lbfa_prefill_paged launch");
 }
 
 }  // extern "C"

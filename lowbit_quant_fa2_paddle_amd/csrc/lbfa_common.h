@@ -310,4 +310,16 @@ struct PoolParams {
 struct PagedDecodeParams : DecodeParams, PoolParams {};
 struct PagedAppendParams : AppendParams, PoolParams {};  // cap = max_pages * page_size
 
+// cached prefill (attn_prefill.hip): the decode call for any Sq, plus ragged query lengths; nQ = ceil(Sq / 128) Q blocks per
+// (batch, query head), `splits` key slices of the tiles each Q block can see.  The partials are the decode kernel's (same M, same
+// rows), so launch_attn_decode_combine takes these structs as the DecodeParams they extend.
+struct PrefillParams : DecodeParams {
+  const int* q_lens;  // [B] or null (every sequence owns all Sq rows)
+  int nQ;
+};
+struct PagedPrefillParams : PagedDecodeParams {
+  const int* q_lens;
+  int nQ;
+};
+
 }  // namespace lbfa

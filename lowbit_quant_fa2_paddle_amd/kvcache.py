@@ -1,4 +1,4 @@
-"""Int8 KV cache and split-KV decode attention for short queries (torch, forward only).
+"""Int8 KV cache, split-KV decode attention for short queries and cached prefill for any number of them (torch, forward only).
 
 `LowbitKVCache` keeps K as the int8 codes and per-64-key scales the dense operators' K quantiser produces (bit for bit: a
 prefill appended to an empty cache holds exactly the codes `lowbit_fa_qk_int8_pv_fp16_triton` would compute), V as fp16, and
@@ -9,8 +9,13 @@ head) to the cache with one split-KV kernel (`lbfa_decode`): K and V are read on
 (`lbfa_kvcache_paged_append`, `lbfa_decode_paged`): sequences of any length share the pool, a finished one gives its pages back,
 and every sequence has a smooth-K mean of its own.  State and decode results equal the contiguous cache's bit for bit.
 
-Not here: prefix sharing / copy-on-write between sequences, an fp8 V cache (its per-channel scale needs the whole sequence), nibble-packed int4
-(the +-7 codes take a byte each), a backward through the cache, Paddle tensors.
+`lowbit_fa_prefill` attends ANY number of new queries to either cache (`lbfa_prefill`, `lbfa_prefill_paged`): chunked prefill of
+a long prompt, the next turn over a cached prefix, a verify step of more than 64 rows.  Q is quantised in the kernel in the dense
+operators' 128-row blocks, the causal mask is bottom-right aligned, query and key lengths are ragged device tensors.
+
+Not here: prefix sharing / copy-on-write between sequences, an fp8 V cache and fp8 PV over the cache (the per-channel scale needs
+the whole sequence), nibble-packed int4 (the +-7 codes take a byte each), a backward through the cache, Paddle tensors, routing
+`lowbit_fa_decode` calls with more than 64 rows to the prefill kernel (decode keeps refusing them).
 """
 from __future__ import annotations
 
@@ -338,19 +343,12 @@ class LowbitPagedKVCache:
                 self.v[idx].transpose(0, 1).reshape(H, -1, D).contiguous())
 
 
-def lowbit_fa_decode(q, cache, tensor_layout: str = "HND", is_causal: bool = False,
-                     sm_scale: Optional[float] = None, return_lse: bool = False, num_splits: int = 0, q_bits: int = 8,
-                     slots=None):
-    """Attention of the new queries q [B, Hq, Sq, D] ("HND") or [B, Sq, Hq, D] ("NHD") to everything in `cache` (the keys of
-    these queries appended first).  Sq * (Hq / Hkv) <= 64.  `is_causal`: bottom-right aligned, query i sees keys
-    < seqlens[b] - Sq + 1 + i.  `num_splits`: key slices (0: chosen by `lbfa_decode_num_splits`); results are bitwise
-    reproducible for a given value.  Returns o (shape and dtype of q) and, with `return_lse`, the natural-log LSE [B, Hq, Sq]
-    fp32.  A sequence with no keys gets zeros and -inf.  Forward only.
-    `cache` is a `LowbitKVCache` or a `LowbitPagedKVCache`; with a paged one row b of q attends to the sequence in
-    `slots[b]` (distinct ints; None: all slots in order)."""
+def _attend(who: str, q, cache, tensor_layout, is_causal, sm_scale, return_lse, num_splits, q_bits, slots, q_lens, prefill: bool):
+    """What `lowbit_fa_decode` and `lowbit_fa_prefill` share: the checks, the padding, the workspace and the argument lists of
+    the contiguous and the paged entry point.  `prefill` picks lbfa_prefill[_paged] (any Sq, `q_lens`) over lbfa_decode[_paged]."""
     ops = ops_for(q)
     if ops.name != "torch":
-        raise TypeError("lowbit_fa_decode takes torch tensors")
+        raise TypeError(f"{who} takes torch tensors")
     torch = ops.torch
     paged = isinstance(cache, LowbitPagedKVCache)
     if not paged and not isinstance(cache, LowbitKVCache):
@@ -358,7 +356,7 @@ def lowbit_fa_decode(q, cache, tensor_layout: str = "HND", is_causal: bool = Fal
     if slots is not None and not paged:
         raise ValueError("slots address the sequences of a LowbitPagedKVCache; a LowbitKVCache is decoded as a whole batch")
     if torch.is_grad_enabled() and q.requires_grad:
-        raise RuntimeError("lowbit_fa_decode is forward-only: there is no backward through the KV cache "
+        raise RuntimeError(f"{who} is forward-only: there is no backward through the KV cache "
                            "(call it under torch.no_grad() or detach q)")
     if tensor_layout not in ("HND", "NHD"):
         raise ValueError(f"Unknown tensor layout: {tensor_layout}")
@@ -384,6 +382,13 @@ def lowbit_fa_decode(q, cache, tensor_layout: str = "HND", is_causal: bool = Fal
         slot_list = _slot_list(slots, B, cache.max_seqs)
     elif B != cache.batch:
         raise ValueError(f"expected batch {cache.batch}, got {B}")
+    if q_lens is not None:
+        try:  # a tensor, or anything torch.as_tensor takes (a list, a numpy array)
+            q_lens = torch.as_tensor(q_lens).to(device=cache.device, dtype=torch.int32).contiguous()
+        except (TypeError, ValueError, RuntimeError) as e:
+            raise TypeError(f"q_lens must be an integer tensor or sequence with one entry per row of q: {e}") from e
+        if tuple(q_lens.shape) != (B,):
+            raise ValueError("q_lens must have one entry per row of q")
     o = ops.empty(qshape, q.dtype, q)
     (_, _, _), o3 = _qpb._bhs(qshape, ops.strides(o), tensor_layout)
     lse = ops.empty((B, Hq, Sq), ops.float32, q) if return_lse else None
@@ -392,26 +397,70 @@ def lowbit_fa_decode(q, cache, tensor_layout: str = "HND", is_causal: bool = Fal
     lib = _lib.load()
     Hkv, D = cache.num_kv_heads, cache.padded_head_dim
     max_k = max(1, min(cache.max_seqlen(slot_list), cache.allocator.capacity) if paged else min(cache.max_seqlen, cache.capacity))
-    ws_bytes = lib.lbfa_decode_workspace_bytes(B, Hq, Hkv, Sq, D, max_k, int(num_splits))
+    workspace_bytes = lib.lbfa_prefill_workspace_bytes if prefill else lib.lbfa_decode_workspace_bytes
+    ws_bytes = workspace_bytes(B, Hq, Hkv, Sq, D, max_k, int(num_splits))
     ws = ops.empty((max(ws_bytes, 16),), ops.uint8, q)
     with ops.device_guard(q):
-        # The arguments the two entry points share, in the order of include/lowbit_fa.h:
+        # The arguments the entry points share, in the order of include/lowbit_fa.h:
         #   lbfa_decode:        head (q .. seqlens), out (o .. D), capacity, rest (max_seqlen_k .. stream)
         #   lbfa_decode_paged:  head, block_table, slots, out, num_slots .. max_pages_per_seq, rest
+        #   lbfa_prefill[_paged]: the same with q_lens behind seqlens
         head = (q.data_ptr(), ops.dtype_code(q), cache.k_codes.data_ptr(), cache.k_scale.data_ptr(), cache.v.data_ptr(),
                 cache.km.data_ptr() if cache.km is not None else None, cache.seqlens.data_ptr())
+        if prefill:
+            head += (q_lens.data_ptr() if q_lens is not None else None,)
         out = (o.data_ptr(), lse.data_ptr() if return_lse else None, ws.data_ptr(), ws_bytes, B, Hq, Hkv, Sq, D)
         rest = (max_k, int(num_splits), _lib.strides3(q3), _lib.strides3(o3), float(sm_scale), 127 if q_bits == 8 else 7,
                 1 if is_causal else 0, ops.stream(q))
         if paged:
             slot_t = torch.tensor(slot_list, dtype=torch.int32, device=cache.device) if slots is not None else None
-            status = lib.lbfa_decode_paged(*head, cache.block_table.data_ptr(), slot_t.data_ptr() if slot_t is not None else None,
-                                           *out, cache.max_seqs, cache.num_pages, cache.page_size, cache.max_pages_per_seq, *rest)
+            entry = lib.lbfa_prefill_paged if prefill else lib.lbfa_decode_paged
+            status = entry(*head, cache.block_table.data_ptr(), slot_t.data_ptr() if slot_t is not None else None,
+                           *out, cache.max_seqs, cache.num_pages, cache.page_size, cache.max_pages_per_seq, *rest)
         else:
-            status = lib.lbfa_decode(*head, *out, cache.capacity, *rest)
+            entry = lib.lbfa_prefill if prefill else lib.lbfa_decode
+            status = entry(*head, *out, cache.capacity, *rest)
         _lib.check(status, lib)
     o = o[..., :head_dim_og]
     return (o, lse) if return_lse else o
 
 
+def lowbit_fa_decode(q, cache, tensor_layout: str = "HND", is_causal: bool = False,
+                     sm_scale: Optional[float] = None, return_lse: bool = False, num_splits: int = 0, q_bits: int = 8,
+                     slots=None):
+    """Attention of the new queries q [B, Hq, Sq, D] ("HND") or [B, Sq, Hq, D] ("NHD") to everything in `cache` (the keys of
+    these queries appended first).  Sq * (Hq / Hkv) <= 64.  `is_causal`: bottom-right aligned, query i sees keys
+    < seqlens[b] - Sq + 1 + i.  `num_splits`: key slices (0: chosen by `lbfa_decode_num_splits`); results are bitwise
+    reproducible for a given value.  Returns o (shape and dtype of q) and, with `return_lse`, the natural-log LSE [B, Hq, Sq]
+    fp32.  A sequence with no keys gets zeros and -inf.  Forward only.
+    `cache` is a `LowbitKVCache` or a `LowbitPagedKVCache`; with a paged one row b of q attends to the sequence in
+    `slots[b]` (distinct ints; None: all slots in order)."""
+    return _attend("lowbit_fa_decode", q, cache, tensor_layout, is_causal, sm_scale, return_lse, num_splits, q_bits, slots, None,
+                   False)
+
+
+def lowbit_fa_prefill(q, cache, tensor_layout: str = "HND", is_causal: bool = False,
+                      sm_scale: Optional[float] = None, return_lse: bool = False, num_splits: int = 0, q_bits: int = 8,
+                      slots=None, q_lens=None):
+    """Cached prefill: attention of ANY number of new queries q [B, Hq, Sq, D] ("HND") or [B, Sq, Hq, D] ("NHD") to everything in
+    `cache` (the keys of these queries appended first) - a chunk of a long prompt, the next turn of a conversation, a
+    speculative-decoding verify step.  For Sq * (Hq / Hkv) <= 64 call `lowbit_fa_decode`.
+
+    `q_lens`: int32 tensor [B] or None (all Sq) - sequence b owns the first q_lens[b] rows of q[b] (clamped to [0, Sq] on the
+    device), the counterpart of `append(..., new_lens=)`; rows at or past it come back as zeros with LSE -inf, and the result
+    for sequence b equals the call on q[b, :, :q_lens[b]] alone.  Keys at or past `cache.seqlens[b]` are masked.
+    Q is quantised inside the kernel in blocks of 128 rows from row 0 of each (batch, head), the last block cut at q_lens[b]:
+    codes and scales are those of the dense operators' Q quantiser on the valid rows (`q_bits` 8 or 4), so a cache filled by one
+    uniform append and read with Sq == Sk sees exactly the dense operator's Q and K codes.  The arithmetic is the decode kernel's:
+    int8 scores x q_scale x k_scale, base-2 online softmax, P rounded to fp16, fp16 MFMA against V, fp32 accumulation.
+    `is_causal`: bottom-right aligned, query i of sequence b sees keys < seqlens[b] - q_lens[b] + 1 + i; a query that sees no
+    key gives zeros and -inf.  `num_splits`: key slices over the tiles a Q block can see (0: chosen by
+    `lbfa_prefill_num_splits`); results are bitwise reproducible for a given value, and equal between a `LowbitKVCache` and a
+    `LowbitPagedKVCache` (`slots` as in `lowbit_fa_decode`).  Returns o (shape and dtype of q) and, with `return_lse`, the
+    natural-log LSE [B, Hq, Sq] fp32 including the smooth-K correction.  Forward only, torch tensors only."""
+    return _attend("lowbit_fa_prefill", q, cache, tensor_layout, is_causal, sm_scale, return_lse, num_splits, q_bits, slots,
+                   q_lens, True)
+
+
 sageattn_decode = lowbit_fa_decode
+sageattn_prefill = lowbit_fa_prefill
