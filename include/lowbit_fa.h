@@ -487,6 +487,62 @@ int lbfa_prefill_paged(const void* q, int dtype, const int8_t* k_codes, const fl
                        const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal,
                        void* stream);
 
+/* ---- fp8 V cache: V as e4m3 codes with one scale per key (additive to ABI 200) ------------------------------------------
+ * The decode kernel streams 3 D bytes per key and kv head, 2 D of them fp16 V.  With V kept as OCP e4m3fn codes and ONE fp32
+ * scale per key and kv head the stream is 2 D + 4 bytes, and the cache takes about two thirds of the memory.  A scale per key
+ * depends on nothing but the row itself: a row is written once, never re-quantised, needs no tail buffer and is paged exactly as
+ * the codes are.  The K state (k_codes, k_scale, k_tail, km, seqlens) is what it is in the fp16-V cache, bit for bit.
+ *
+ * Format.  v_cache is uint8 [B, Hkv, capacity, D] (paged: [num_pages, Hkv, page_size, D]), v_scale fp32 [B, Hkv, capacity]
+ * (paged: [num_pages, Hkv, page_size], found from the same pool tile as codes and V).  The quantiser of one appended row works on
+ * its D channels, all in fp32:
+ *     x = fp32(v);  amax = max(max |x|, 1e-7);  scale = amax / 448 (correctly rounded);  code = e4m3fn_rne(x / scale).
+ * |x / scale| <= 448 (1 + 2^-23), so no code depends on saturation.  Code and scale of a row never change after they are
+ * written: any append schedule gives the state of a one-shot append, bit for bit.
+ *
+ * What a reader sees is  V^ = fp16_rne(fp32(decode(code)) * scale) : one fp32 multiply and one round-to-nearest-even conversion
+ * per element, fp16 subnormals kept.  For finite input |V^ - V| <= (2^-4 + 2^-10) |V| + 2^-10 scale + 2^-24 per element; a bf16
+ * magnitude past 65504 becomes inf as it does in the fp16 cache; non-finite V rows are outside the contract and do not disturb
+ * other rows.  A read of an fp8 cache equals, bit for bit, the same read of an fp16 cache whose V holds V^, for the same
+ * num_splits, contiguous or paged: the tile is turned into V^ on its way into the LDS image, everything behind it is the fp16
+ * kernel (rows at or past the length enter as zeros whatever their codes and scales are).
+ *
+ * Each entry point has the contract, the refusals and the device-side defences of its sibling without the suffix (lengths
+ * clamped; slot and page ids clamped for the reads and skipped for the appends; appends clipped at the capacity), the same
+ * lbfa_decode_num_splits / lbfa_prefill_num_splits rules and workspace sizes.  The argument lists are the siblings' with v_cache
+ * as uint8_t* and v_scale directly behind it.  Two more refusals: a NULL v_scale ("null pointer") and a v_scale that is not
+ * 16-byte aligned, both LBFA_EINVAL.
+ */
+int lbfa_kvcache_append_v8(const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
+                           int8_t* k_codes, float* k_scale, uint8_t* v_cache, float* v_scale, void* k_tail, const int32_t* seqlens,
+                           int B, int Hkv, int T, int D, int capacity, const int64_t strides_k[3], const int64_t strides_v[3],
+                           int k_qmax, void* stream);
+int lbfa_kvcache_paged_append_v8(const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
+                                 int8_t* k_codes, float* k_scale, uint8_t* v_cache, float* v_scale, void* k_tail,
+                                 const int32_t* seqlens, const int32_t* block_table, const int32_t* slots, int B, int Hkv, int T,
+                                 int D, int num_slots, int num_pages, int page_size, int max_pages_per_seq,
+                                 const int64_t strides_k[3], const int64_t strides_v[3], int k_qmax, void* stream);
+int lbfa_decode_v8(const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const uint8_t* v_cache, const float* v_scale,
+                   const void* km, const int32_t* seqlens, void* o, float* lse, void* workspace, size_t workspace_bytes,
+                   int B, int Hq, int Hkv, int Sq, int D, int capacity, int max_seqlen_k, int num_splits,
+                   const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream);
+int lbfa_decode_paged_v8(const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const uint8_t* v_cache,
+                         const float* v_scale, const void* km, const int32_t* seqlens, const int32_t* block_table,
+                         const int32_t* slots, void* o, float* lse, void* workspace, size_t workspace_bytes, int B, int Hq, int Hkv,
+                         int Sq, int D, int num_slots, int num_pages, int page_size, int max_pages_per_seq, int max_seqlen_k,
+                         int num_splits, const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax,
+                         int is_causal, void* stream);
+int lbfa_prefill_v8(const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const uint8_t* v_cache, const float* v_scale,
+                    const void* km, const int32_t* seqlens, const int32_t* q_lens, void* o, float* lse, void* workspace,
+                    size_t workspace_bytes, int B, int Hq, int Hkv, int Sq, int D, int capacity, int max_seqlen_k, int num_splits,
+                    const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream);
+int lbfa_prefill_paged_v8(const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const uint8_t* v_cache,
+                          const float* v_scale, const void* km, const int32_t* seqlens, const int32_t* q_lens,
+                          const int32_t* block_table, const int32_t* slots, void* o, float* lse, void* workspace,
+                          size_t workspace_bytes, int B, int Hq, int Hkv, int Sq, int D, int num_slots, int num_pages, int page_size,
+                          int max_pages_per_seq, int max_seqlen_k, int num_splits, const int64_t strides_q[3],
+                          const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,6 +94,11 @@ SIGNATURES = {
                                  _ci, _ci, _ci, _ci, _ci, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _cd, _ci, _ci,
                                  _vp]),
 }
+# the fp8 V cache: each entry point's sibling with `v_scale` directly behind `v_cache` (argument 8 of the appends, 5 of the readers)
+for _name, _at in (("lbfa_kvcache_append", 8), ("lbfa_kvcache_paged_append", 8), ("lbfa_decode", 5), ("lbfa_decode_paged", 5),
+                   ("lbfa_prefill", 5), ("lbfa_prefill_paged", 5)):
+    _res, _args = SIGNATURES[_name]
+    SIGNATURES[_name + "_v8"] = (_res, _args[:_at] + [_vp] + _args[_at:])
 
 _lock = threading.Lock()
 _lib = None

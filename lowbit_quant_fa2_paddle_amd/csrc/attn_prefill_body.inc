@@ -1,0 +1,264 @@
+// Body of attn_prefill_kernel / attn_prefill_v8_kernel (attn_prefill.hip), included as text inside each with the kernel's template parameters, its parameter
+// block `p` and `constexpr int VB` (bits of a cached V element: 16 or 8) in scope.  See attn_prefill.hip.
+  constexpr int MB = 2;             // 16-row blocks per wave
+  constexpr int KS = D / 64;        // k-steps of the score product
+  constexpr int CB = D / 16;        // 16-channel blocks of O^T
+  constexpr int VROW = 2 * D + 32;  // bytes per LDS row
+  constexpr int VCH = D * VB / 512;  // 16-byte chunks of a V tile per thread
+  typedef VStage<VCH, VB == 8 ? VCH : 0> vstage_t;  // fp8 V: and the scale of each chunk's key
+  typedef typename KV::tile_t tile_t;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[64 * VROW];
+  __shared__ float wamax[4];
+  const int qblk = blockIdx.x / p.splits, split = blockIdx.x - qblk * p.splits;
+  const int h = blockIdx.y, b = blockIdx.z, hk = h / p.group;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i16 = lane & 15, g = lane >> 4;
+  const KV kv(p, b, hk, D);
+  const int n = min(max(p.seqlens[kv.slot], 0), p.max_k);
+  const int ql = p.q_lens != nullptr ? min(max(p.q_lens[b], 0), p.Sq) : p.Sq;
+  // tiles this Q block can see: below the limit of its last valid row (none: the block lies past the sequence's queries)
+  const int last = min(qblk * 128 + 127, ql - 1);
+  const int see = last < qblk * 128 ? 0 : (p.causal ? max(n - ql + 1 + last, 0) : n);
+  const int ntiles = (see + 63) >> 6;
+  const int tps = (ntiles + p.splits - 1) / p.splits;
+  const int t0 = split * tps, t1 = min(t0 + tps, ntiles);
+  const int64_t sh = (int64_t)kv.slot * p.Hkv + hk;  // (slot, kv head): km
+
+  // ---- query rows of this lane: load, quantise with the block's scale, q . km ------------------------------------------
+  int row[MB], lim[MB];
+  i32x4 qf[MB][KS];
+  float corr[MB];
+  float qsc;
+  {
+    float xq[MB][KS][16];
+    float amax = 0.f;
+#pragma unroll
+    for (int rb = 0; rb < MB; ++rb) {
+      row[rb] = qblk * 128 + wave * 32 + 16 * rb + i16;
+      const bool valid = row[rb] < ql;
+      lim[rb] = valid ? (p.causal ? n - ql + 1 + row[rb] : n) : 0;
+      float dot = 0.f;
+      const unsigned short* qp = p.q + (int64_t)b * p.qb + (int64_t)h * p.qh + (int64_t)(valid ? row[rb] : 0) * p.qs + 16 * g;
+#pragma unroll
+      for (int s = 0; s < KS; ++s) {
+        uint4 raw[2] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
+        if (valid) {
+          raw[0] = *reinterpret_cast<const uint4*>(qp + 64 * s);
+          raw[1] = *reinterpret_cast<const uint4*>(qp + 64 * s + 8);
+        }
+        uint4 kmr[2] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
+        if (p.km != nullptr) {
+          kmr[0] = *reinterpret_cast<const uint4*>(p.km + sh * D + 64 * s + 16 * g);
+          kmr[1] = *reinterpret_cast<const uint4*>(p.km + sh * D + 64 * s + 16 * g + 8);
+        }
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float v = elem16<DT>(raw[hf], e);
+            dot += v * elem16<DT>(kmr[hf], e);
+            const float x = v * p.q_sm_scale;
+            xq[rb][s][hf * 8 + e] = x;
+            amax = fmaxf(amax, fabsf(x));
+          }
+      }
+      dot += __shfl_xor(dot, 16, 64);
+      dot += __shfl_xor(dot, 32, 64);
+      corr[rb] = load_cvt<DT>(store_cvt<DT>(dot));  // the correction is a storage-dtype matmul (src/core.py:294-304)
+    }
+    amax = wave_max(amax);
+    if (lane == 0) wamax[wave] = amax;
+    __syncthreads();
+    qsc = block_scale(amax_collect(wamax), p.q_qmax);
+#pragma unroll
+    for (int rb = 0; rb < MB; ++rb)
+#pragma unroll
+      for (int s = 0; s < KS; ++s) qf[rb][s] = quant_codes16<false>(xq[rb][s], qsc, 0.f);  // the plain division
+  }
+  // the compare against the row limits is needed only in tiles that reach past the smallest limit of this wave's rows
+  const int lim_min = wave_min_i32(min(lim[0], lim[1]));
+
+  // ---- running state ---------------------------------------------------------------------------------------------------
+  f32x4 acc[MB][CB];
+  float m_run[MB], l_run[MB];
+#pragma unroll
+  for (int rb = 0; rb < MB; ++rb) {
+    m_run[rb] = -__builtin_inff();
+    l_run[rb] = 0.f;
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) acc[rb][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+
+  const int8_t* kbase = kv.codes + (int64_t)i16 * D + 16 * g;
+  const unsigned short* vbase = kv.v;
+  const float* ksc = kv.scale;
+  typedef __attribute__((address_space(3))) unsigned char lds_byte;
+  typedef __attribute__((address_space(3))) s16x4v lds_s16x4;
+  lds_byte* const vt_lane = (lds_byte*)smem + (4 * g + (i16 >> 2)) * VROW + (i16 & 3) * 8;
+
+  auto load_k = [&](tile_t t, i32x4 (&kf)[4][KS]) __attribute__((always_inline)) {
+    const int8_t* kt = kbase + (int64_t)t * 64 * D;
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+      for (int s = 0; s < KS; ++s) kf[kb][s] = *reinterpret_cast<const i32x4*>(kt + kb * 16 * D + 64 * s);
+  };
+  const uint8_t* v8base = nullptr;  // fp8 V: the codes and the scales of (b, hk), or of the pool
+  const float* vsbase = nullptr;
+  if constexpr (VB == 8) {
+    const int64_t key0 = KV::key0(p, b, hk);
+    v8base = reinterpret_cast<const uint8_t*>(p.v) + key0 * D;
+    vsbase = p.v_scale + key0;
+  }
+  auto load_v = [&](tile_t t, vstage_t& vr) __attribute__((always_inline)) {
+    if constexpr (VB == 8) {
+      const uint8_t* vt = v8base + (int64_t)t * 64 * D;
+#pragma unroll
+      for (int u = 0; u < VCH; ++u) load_v8_chunk<D>(vt, vsbase + (int64_t)t * 64, u * 256 + tid, vr.c[u], vr.s[u]);
+    } else {
+      const unsigned short* vt = vbase + (int64_t)t * 64 * D;
+#pragma unroll
+      for (int u = 0; u < VCH; ++u) vr.c[u] = *reinterpret_cast<const uint4*>(vt + (u * 256 + tid) * 8);  // the tile is contiguous
+    }
+  };
+  auto store_v = [&](int t, const vstage_t& vr) __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < VCH; ++u) {
+      if constexpr (VB == 8) {
+        store_vhat_chunk<D, VROW>(smem, u * 256 + tid, vr.c[u], vr.s[u], n - t * 64);
+      } else {
+        const int cidx = u * 256 + tid, r = cidx / (D / 8), ch = cidx % (D / 8);
+        // rows past the end may hold anything (0 * NaN): they enter the product as zeros
+        const uint4 val = (t * 64 + r < n) ? vr.c[u] : make_uint4(0, 0, 0, 0);
+        *reinterpret_cast<uint4*>(smem + r * VROW + ch * 16) = val;
+      }
+    }
+  };
+  auto compute = [&](int t, tile_t gt, const i32x4 (&kf)[4][KS], auto masked) __attribute__((always_inline)) {
+    constexpr bool MASK = decltype(masked)::value;
+    const float kscale = ksc[gt];
+#pragma unroll
+    for (int rb = 0; rb < MB; ++rb) {
+      float sc[4][4];
+      float tmax = -__builtin_inff();
+#pragma unroll
+      for (int kb = 0; kb < 4; ++kb) {
+        i32x4 sacc = i32x4{0, 0, 0, 0};
+#pragma unroll
+        for (int s = 0; s < KS; ++s) sacc = __builtin_amdgcn_mfma_i32_16x16x64_i8(kf[kb][s], qf[rb][s], sacc, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float s2 = (float)sacc[r] * qsc * kscale;
+          if constexpr (MASK) s2 = t * 64 + kb * 16 + 4 * g + r < lim[rb] ? s2 : -__builtin_inff();
+          sc[kb][r] = s2;
+          tmax = fmaxf(tmax, s2);
+        }
+      }
+      tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
+      tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+      const float m_new = fmaxf(m_run[rb], tmax);
+      const float m_use = m_new == -__builtin_inff() ? 0.f : m_new;  // a row with no visible key yet: p = 0, no NaN
+      const float alpha = __builtin_amdgcn_exp2f(m_run[rb] - m_use);
+      float lsum = 0.f;
+      f16x8 pf[2];
+#pragma unroll
+      for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float pe = __builtin_amdgcn_exp2f(sc[kb][r] - m_use);
+          lsum += pe;
+          pf[kb >> 1][(kb & 1) * 4 + r] = (_Float16)pe;
+        }
+      lsum += __shfl_xor(lsum, 16, 64);
+      lsum += __shfl_xor(lsum, 32, 64);
+      l_run[rb] = l_run[rb] * alpha + lsum;
+      m_run[rb] = m_new;
+#pragma unroll
+      for (int cb = 0; cb < CB; ++cb) {
+        acc[rb][cb] *= alpha;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          const s16x4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vt_lane + (32 * s) * VROW + cb * 32));
+          const s16x4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vt_lane + (32 * s + 16) * VROW + cb * 32));
+          const f16x4 lo16 = __builtin_bit_cast(f16x4, lo), hi16 = __builtin_bit_cast(f16x4, hi);
+          const f16x8 vf = f16x8{lo16[0], lo16[1], lo16[2], lo16[3], hi16[0], hi16[1], hi16[2], hi16[3]};
+          acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pf[s], acc[rb][cb], 0, 0, 0);
+        }
+      }
+    }
+  };
+  // wave-uniform: a tile wholly below every limit of the wave's rows takes the form without the compare (same bits)
+  auto tile = [&](int t, tile_t gt, const i32x4 (&kf)[4][KS]) __attribute__((always_inline)) {
+    if (t * 64 + 64 <= lim_min) compute(t, gt, kf, std::false_type{});
+    else compute(t, gt, kf, std::true_type{});
+  };
+
+  // ---- tile loop: K of tile t + 1 lands in the other register set, V of tile t + 1 in registers, while tile t is computed.
+  // The look-ahead index is clamped to the slice (the last tile is requested twice, from cache) so no load sits in a branch; the
+  // page id of the tile after the look-ahead tile is fetched one step early (ContiguousKV: fetch() is nothing, locate(t) = t).
+  // All four waves take every barrier: t0, t1 depend on the workgroup only.
+  if (t0 < t1) {
+    i32x4 ka[4][KS], kb_[4][KS];
+    vstage_t vr;
+    tile_t ga = kv.locate(t0, kv.fetch(t0)), gb;
+    int pn = kv.fetch(min(t0 + 1, t1 - 1));
+    load_k(ga, ka);
+    load_v(ga, vr);
+    store_v(t0, vr);
+    __syncthreads();
+    for (int t = t0; t < t1; t += 2) {
+      const int ta = min(t + 1, t1 - 1);
+      gb = kv.locate(ta, pn);
+      pn = kv.fetch(min(t + 2, t1 - 1));
+      load_k(gb, kb_);
+      load_v(gb, vr);
+      tile(t, ga, ka);
+      __syncthreads();
+      if (t + 1 >= t1) break;
+      store_v(ta, vr);
+      __syncthreads();
+      const int tb = min(t + 2, t1 - 1);
+      ga = kv.locate(tb, pn);
+      pn = kv.fetch(min(t + 3, t1 - 1));
+      load_k(ga, ka);
+      load_v(ga, vr);
+      tile(t + 1, gb, kb_);
+      __syncthreads();
+      store_v(tb, vr);
+      __syncthreads();
+    }
+  }
+
+  // ---- epilogue: rows past Sq do not exist; rows in [q_lens[b], Sq) saw no key: zeros, -inf ----------------------------------
+  if (p.splits == 1) {
+#pragma unroll
+    for (int rb = 0; rb < MB; ++rb) {
+      if (row[rb] >= p.Sq) continue;
+      const float l = l_run[rb];
+      const float inv = l > 0.f ? 1.0f / l : 0.f;  // no visible key: zeros, LSE -inf (as the varlen operator)
+      unsigned short* op = reinterpret_cast<unsigned short*>(p.o) + (int64_t)b * p.ob + (int64_t)h * p.oh + (int64_t)row[rb] * p.os + 4 * g;
+#pragma unroll
+      for (int cb = 0; cb < CB; ++cb) {
+        const f32x4 a = acc[rb][cb];
+        const unsigned w0 = (unsigned)store_cvt<DT>(a[0] * inv) | ((unsigned)store_cvt<DT>(a[1] * inv) << 16);
+        const unsigned w1 = (unsigned)store_cvt<DT>(a[2] * inv) | ((unsigned)store_cvt<DT>(a[3] * inv) << 16);
+        *reinterpret_cast<uint2*>(op + 16 * cb) = make_uint2(w0, w1);
+      }
+      if (p.lse != nullptr && g == 0) {
+        const float lse2 = l > 0.f ? __builtin_amdgcn_logf(l) + m_run[rb] : -__builtin_inff();
+        p.lse[((int64_t)b * p.Hq + h) * p.Sq + row[rb]] = lse2 / kLog2e + corr[rb] * p.corr_scale;
+      }
+    }
+  } else {
+    const int64_t bh = (int64_t)b * p.Hkv + hk;  // (row of the call, kv head): the partials
+    const int64_t slot = (bh * p.splits + split) * p.M + (int64_t)(h - hk * p.group) * p.Sq;
+#pragma unroll
+    for (int rb = 0; rb < MB; ++rb) {
+      if (row[rb] >= p.Sq) continue;
+      if (t0 < t1) {  // the combine never reads the acc of a slice whose m is -inf
+        float* ap = p.ws_acc + (slot + row[rb]) * D + 4 * g;
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) *reinterpret_cast<f32x4*>(ap + 16 * cb) = acc[rb][cb];
+      }
+      if (g == 0) *reinterpret_cast<f32x4*>(p.ws_ml + (slot + row[rb]) * 4) = f32x4{m_run[rb], l_run[rb], corr[rb], 0.f};
+    }
+  }

@@ -8,7 +8,7 @@ namespace lbfa {
 typedef short s16x4v __attribute__((ext_vector_type(4)));
 constexpr float kLog2e = 1.44269504f;  // the literal of src/core.py:347; the natural-log LSE is a correctly rounded division by it
 
-// Contiguous cache: k_codes int8 / v fp16 [B, Hkv, cap, D], k_scale fp32 [B, Hkv, cap / 64].  Tile t of (b, hk) is tile t behind
+// Contiguous cache: k_codes int8 / v fp16 (fp8 V cache: e4m3 codes, see below) [B, Hkv, cap, D], k_scale fp32 [B, Hkv, cap / 64].  Tile t of (b, hk) is tile t behind
 // the bases of that (b, hk); seqlens and km are indexed by the row of the call.
 struct ContiguousKV {
   typedef DecodeParams Params;
@@ -25,6 +25,8 @@ struct ContiguousKV {
     v = p.v + bh * (int64_t)p.cap * D;
     scale = p.k_scale + bh * (p.cap >> 6);
   }
+  // first key of (b, hk) in an array with one entry per key: the codes and the scales of the fp8 V cache
+  static __device__ __forceinline__ int64_t key0(const Params& p, int b, int hk) { return ((int64_t)b * p.Hkv + hk) * (int64_t)p.cap; }
   __device__ __forceinline__ int fetch(int) const { return 0; }
   __device__ __forceinline__ tile_t locate(int t, int) const { return t; }
 };
@@ -61,11 +63,63 @@ struct PagedKV {
     Hkv = p.Hkv;
     num_pages = p.num_pages;
   }
+  static __device__ __forceinline__ int64_t key0(const Params&, int, int) { return 0; }  // tiles are numbered in the pool
   __device__ __forceinline__ int fetch(int t) const { return tbl[t / tpp]; }
   __device__ __forceinline__ tile_t locate(int t, int pg) const {
     pg = __builtin_amdgcn_readfirstlane(min(max(pg, 0), num_pages - 1));
     return ((int64_t)pg * Hkv + hk) * tpp + t % tpp;
   }
 };
+
+
+// ---- the fp8 V cache (v_bits = 8): V as e4m3fn codes [.., key, D] with ONE fp32 scale per key and kv head, written by the
+// append kernel (kvcache.hip) and never re-quantised.  What a reader sees is V^ = fp16_rne(fp32(decode(code)) * scale): one fp32
+// multiply and one round-to-nearest-even conversion per element, fp16 subnormals kept.  The readers turn a tile into V^ on its
+// way into the LDS image the fp16 V tile has; everything behind the image is the fp16 code.
+// What a thread keeps of the V tile that is on its way: NC 16-byte chunks and - fp8 V - NS scales
+template <int NC, int NS>
+struct VStage {
+  uint4 c[NC];
+  float s[NS];
+};
+template <int NC>
+struct VStage<NC, 0> {
+  uint4 c[NC];
+};
+// 16 codes of one key (a 16-byte chunk) -> their 16 V^ as two 16-byte chunks of fp16
+__device__ __forceinline__ void e4m3x16_to_vhat(const uint4& codes, float scale, uint4& lo, uint4& hi) {
+  const unsigned w[4] = {codes.x, codes.y, codes.z, codes.w};
+  unsigned o[8];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
+    const f16x2 pa = f16x2{(_Float16)(a[0] * scale), (_Float16)(a[1] * scale)};
+    const f16x2 pb = f16x2{(_Float16)(b[0] * scale), (_Float16)(b[1] * scale)};
+    o[2 * i] = __builtin_bit_cast(unsigned, pa);
+    o[2 * i + 1] = __builtin_bit_cast(unsigned, pb);
+  }
+  lo = make_uint4(o[0], o[1], o[2], o[3]);
+  hi = make_uint4(o[4], o[5], o[6], o[7]);
+}
+
+// A tile of the fp8 V cache is 64 D contiguous code bytes and 64 contiguous scales; chunk `cidx` of it is 16 channels of key
+// cidx / (D / 16).  The two steps of a reader, shared by the decode and the prefill body (their threads differ in which chunks they take):
+// fetch a chunk with the scale of its key ...
+template <int D>
+__device__ __forceinline__ void load_v8_chunk(const uint8_t* tile, const float* scales, int cidx, uint4& codes, float& scale) {
+  codes = *reinterpret_cast<const uint4*>(tile + cidx * 16);
+  scale = scales[cidx / (D / 16)];
+}
+// ... and write its V^ as the two 16-byte chunks the fp16 tile has at that place of the [64][VROW] LDS image.  Keys at or past
+// `valid_keys` may hold any code and any scale (NaN): they enter the product as zeros.
+template <int D, int VROW>
+__device__ __forceinline__ void store_vhat_chunk(unsigned char* image, int cidx, const uint4& codes, float scale, int valid_keys) {
+  const int r = cidx / (D / 16), ch = cidx % (D / 16);
+  uint4 lo, hi;
+  e4m3x16_to_vhat(codes, scale, lo, hi);
+  const bool in = r < valid_keys;
+  *reinterpret_cast<uint4*>(image + r * VROW + ch * 32) = in ? lo : make_uint4(0, 0, 0, 0);
+  *reinterpret_cast<uint4*>(image + r * VROW + ch * 32 + 16) = in ? hi : make_uint4(0, 0, 0, 0);
+}
 
 }  // namespace lbfa

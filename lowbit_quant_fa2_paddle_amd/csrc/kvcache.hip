@@ -62,86 +62,43 @@ struct PagedDst {
   }
 };
 
+// One appended V row as e4m3 codes with a scale of its own (the fp8 V cache, kv_policy.h), all in fp32: x = fp32(v), amax =
+// max(max |x|, 1e-7) over the D channels, scale = amax / 448 (correctly rounded), code = e4m3fn_rne(x / scale).  |x / scale| stays
+// below 448 (1 + 2^-23), so the conversion never depends on how it treats what lies past 464.  The CPR = D / 8 threads that hold the
+// row (consecutive lanes, each 8 channels) reduce the amax among themselves; every one of them must call this.
+template <int DT, int CPR>
+__device__ __forceinline__ uint2 quant_v_row_e4m3(const u32x4& raw, float& scale) {
+  float x[8];
+  unpack8<DT>(raw, x);
+  float amax = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(x[i]));
+#pragma unroll
+  for (int o = 1; o < CPR; o <<= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+  scale = fmaxf(amax, 1e-7f) / 448.f;
+  int w0 = 0, w1 = 0;
+  w0 = __builtin_amdgcn_cvt_pk_fp8_f32(x[0] / scale, x[1] / scale, w0, false);
+  w0 = __builtin_amdgcn_cvt_pk_fp8_f32(x[2] / scale, x[3] / scale, w0, true);
+  w1 = __builtin_amdgcn_cvt_pk_fp8_f32(x[4] / scale, x[5] / scale, w1, false);
+  w1 = __builtin_amdgcn_cvt_pk_fp8_f32(x[6] / scale, x[7] / scale, w1, true);
+  return make_uint2((unsigned)w0, (unsigned)w1);
+}
+
+// The body is written once, in kvcache_append_body.inc, and included as text into both kernels: VB = bits of a cached V element, 16 (fp16) or 8
+// (e4m3 codes with a scale per key, kv_policy.h).  Text, not a function the two kernels call: routed through an inlined function
+// the fp16 instances compile to other code than they had (same instructions, another schedule), and they are the yardstick the fp8
+// family is measured against.  Included, they are the code they were, byte for byte.
+// K is handled the same way in both.
 template <class Dst, int DT, int D>
 __global__ __launch_bounds__(256) void kvcache_append_kernel(typename Dst::Params p) {
-  constexpr int CPR = D / 8;       // 16-byte chunks per row
-  constexpr int RPP = 256 / CPR;   // rows per pass
-  constexpr int NP = 64 / RPP;     // passes per 64-key block
-  __shared__ float wmax[4];
-  const int x = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
-  const int t = threadIdx.x, c = t % CPR, rl = t / CPR;
-  int sl, s0, tb;
-  if (!Dst::slot(p, b, sl)) return;  // workgroup-uniform
-  append_range(p, b, sl, s0, tb);
-  if (tb <= 0) return;  // workgroup-uniform
-  const int first = s0 >> 6, last = (s0 + tb - 1) >> 6;
-  if (x > 0 && first + x >= last) return;
-  const int64_t sh = (int64_t)sl * p.Hkv + h;  // (slot, head): k_tail, km
-  const unsigned short* knew = p.k_new + (int64_t)b * p.kb + (int64_t)h * p.kh + c * 8;
-  const unsigned short* vnew = p.v_new + (int64_t)b * p.vb + (int64_t)h * p.vh + c * 8;
-  unsigned short* tail = p.k_tail + sh * 64 * D + c * 8;
-  float mean[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) mean[i] = 0.f;
-  const bool has_mean = p.km != nullptr;
-  if (has_mean) unpack8<DT>(*reinterpret_cast<const uint4*>(p.km + sh * D + c * 8), mean);
-  const int end = s0 + tb;
-
-  // x = 0: block `first`, then block `last` when it is another one; x >= 1: one middle block
-  const int npass = (x == 0 && last > first) ? 2 : 1;
-  for (int pass = 0; pass < npass; ++pass) {
-    const int blk = x > 0 ? first + x : (pass == 0 ? first : last);
-    const int r0 = blk << 6;
-    int64_t gb;
-    if (!Dst::block(p, sl, h, blk, gb)) continue;     // workgroup-uniform, before the barriers of the pass: the block is skipped
-    int8_t* codes = p.k_codes + gb * 64 * D + c * 8;  // row r0 of the sequence
-    unsigned short* vdst = p.v + gb * 64 * D + c * 8;
-    uint4 raw[NP];
-#pragma unroll
-    for (int ps = 0; ps < NP; ++ps) {
-      const int row = r0 + ps * RPP + rl;
-      raw[ps] = make_uint4(0, 0, 0, 0);
-      if (row < s0) raw[ps] = *reinterpret_cast<const uint4*>(tail + (int64_t)(row - r0) * D);  // only block `first` has such rows
-      else if (row < end) raw[ps] = *reinterpret_cast<const uint4*>(knew + (int64_t)(row - s0) * p.ks);
-    }
-    float xs[NP][8];
-    float amax = 0.f;
-#pragma unroll
-    for (int ps = 0; ps < NP; ++ps) {
-      const int row = r0 + ps * RPP + rl;
-      float v[8];
-      unpack8<DT>(raw[ps], v);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        float xv = v[i];
-        // `k - km` in the storage dtype, rows past the end stay 0: exactly quant_per_block_kernel (sm_scale = 1 for K)
-        if (has_mean) xv = (row < end) ? load_cvt<DT>(store_cvt<DT>(xv - mean[i])) : 0.f;
-        xs[ps][i] = xv;
-        amax = fmaxf(amax, fabsf(xv));
-      }
-    }
-    amax = wave_max_nonneg(amax);
-    if ((t & 63) == 0) wmax[t >> 6] = amax;
-    __syncthreads();  // also: every read of k_tail (pass 0) is done before pass 1 stores to it
-    const float scale = block_scale(amax_collect(wmax), p.qmax);
-    if (t == 0) p.k_scale[gb] = scale;
-    const bool open = (blk == last) && (end & 63) != 0;  // this block is the open one afterwards: keep its raw rows
-#pragma unroll
-    for (int ps = 0; ps < NP; ++ps) {
-      const int row = r0 + ps * RPP + rl;
-      int q[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) q[i] = quant_code<false>(xs[ps][i], scale, 0.f);  // the plain division
-      if (row < end) *reinterpret_cast<uint2*>(codes + (int64_t)(row - r0) * D) = pack8_i8(q);
-      if (row >= s0 && row < end) {
-        if (open) *reinterpret_cast<uint4*>(tail + (int64_t)(row - r0) * D) = raw[ps];
-        u32x4 vr = *reinterpret_cast<const u32x4*>(vnew + (int64_t)(row - s0) * p.vs);
-        if constexpr (DT == LBFA_BF16) vr = bf16x8_to_f16x8(vr);
-        *reinterpret_cast<u32x4*>(vdst + (int64_t)(row - r0) * D) = vr;
-      }
-    }
-    __syncthreads();  // wmax is reused by the second pass
-  }
+  constexpr int VB = 16;
+#include "kvcache_append_body.inc"
+}
+// the same kernel for the fp8 V cache; the name keeps its family apart from the fp16 one in the code object
+template <class Dst, int DT, int D>
+__global__ __launch_bounds__(256) void kvcache_append_v8_kernel(V8Params<typename Dst::Params, float*> p) {
+  constexpr int VB = 8;
+#include "kvcache_append_body.inc"
 }
 
 // Smooth-K mean of a first append whose sequences have different lengths: km[b, h, :] = storage dtype of the fp32 of the float64
@@ -183,20 +140,30 @@ static int kvcache_append_grid_x(int T) {
   return touched > 2 ? touched - 1 : 1;
 }
 
-template <class Dst>
-static hipError_t launch_append(const typename Dst::Params& p, int dtype, int D, hipStream_t stream) {
+template <class Dst, int VB, class P>
+static hipError_t launch_append(const P& p, int dtype, int D, hipStream_t stream) {
   dim3 grid(kvcache_append_grid_x(p.T), p.Hkv, p.B);
-#define LBFA_APP(DT, DD) hipLaunchKernelGGL((kvcache_append_kernel<Dst, DT, DD>), grid, dim3(256), 0, stream, p)
+#define LBFA_APP(DT, DD)                                                                                         \
+  do {                                                                                                           \
+    if constexpr (VB == 8) hipLaunchKernelGGL((kvcache_append_v8_kernel<Dst, DT, DD>), grid, dim3(256), 0, stream, p); \
+    else hipLaunchKernelGGL((kvcache_append_kernel<Dst, DT, DD>), grid, dim3(256), 0, stream, p);                \
+  } while (0)
   if (dtype == LBFA_F16) { if (D == 64) LBFA_APP(LBFA_F16, 64); else LBFA_APP(LBFA_F16, 128); }
   else { if (D == 64) LBFA_APP(LBFA_BF16, 64); else LBFA_APP(LBFA_BF16, 128); }
 #undef LBFA_APP
   return hipGetLastError();
 }
 hipError_t launch_kvcache_append(const AppendParams& p, int dtype, int D, hipStream_t stream) {
-  return launch_append<ContiguousDst>(p, dtype, D, stream);
+  return launch_append<ContiguousDst, 16>(p, dtype, D, stream);
 }
 hipError_t launch_kvcache_paged_append(const PagedAppendParams& p, int dtype, int D, hipStream_t stream) {
-  return launch_append<PagedDst>(p, dtype, D, stream);
+  return launch_append<PagedDst, 16>(p, dtype, D, stream);
+}
+hipError_t launch_kvcache_append_v8(const V8Params<AppendParams, float*>& p, int dtype, int D, hipStream_t stream) {
+  return launch_append<ContiguousDst, 8>(p, dtype, D, stream);
+}
+hipError_t launch_kvcache_paged_append_v8(const V8Params<PagedAppendParams, float*>& p, int dtype, int D, hipStream_t stream) {
+  return launch_append<PagedDst, 8>(p, dtype, D, stream);
 }
 
 hipError_t launch_kvcache_mean(const RaggedMeanParams& p, int dtype, int B, int D, hipStream_t stream) {

@@ -32,6 +32,13 @@ hipError_t launch_attn_paged_decode(const PagedDecodeParams& p, int dtype, int D
 // defined in attn_prefill.hip
 hipError_t launch_attn_prefill(const PrefillParams& p, int dtype, int D, hipStream_t stream);
 hipError_t launch_attn_paged_prefill(const PagedPrefillParams& p, int dtype, int D, hipStream_t stream);
+// the same six over the fp8 V cache (the *_v8_kernel instances)
+hipError_t launch_kvcache_append_v8(const V8Params<AppendParams, float*>& p, int dtype, int D, hipStream_t stream);
+hipError_t launch_kvcache_paged_append_v8(const V8Params<PagedAppendParams, float*>& p, int dtype, int D, hipStream_t stream);
+hipError_t launch_attn_decode_v8(const V8Params<DecodeParams, const float*>& p, int dtype, int D, hipStream_t stream);
+hipError_t launch_attn_paged_decode_v8(const V8Params<PagedDecodeParams, const float*>& p, int dtype, int D, hipStream_t stream);
+hipError_t launch_attn_prefill_v8(const V8Params<PrefillParams, const float*>& p, int dtype, int D, hipStream_t stream);
+hipError_t launch_attn_paged_prefill_v8(const V8Params<PagedPrefillParams, const float*>& p, int dtype, int D, hipStream_t stream);
 }  // namespace lbfa
 
 namespace {
@@ -973,8 +980,11 @@ struct AppendCall {
   const int32_t* seqlens;
   int B, Hkv, T, D, k_qmax;
   Pool pool;
+  // fp8 V cache (the _v8 entry points): v_cache holds e4m3 codes, v_scale one fp32 per key
+  bool v8;
+  float* v_scale;
 };
-// what both append entry points state, in the order of their signatures; `pool` says where the keys live
+// what the append entry points state, in the order of their signatures; `pool` says where the keys live
 AppendCall append_call(const char* who, const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
                        int8_t* k_codes, float* k_scale, void* v_cache, void* k_tail, const int32_t* seqlens, int B, int Hkv, int T,
                        int D, const int64_t strides_k[3], const int64_t strides_v[3], int k_qmax, const Pool& pool) {
@@ -986,7 +996,8 @@ AppendCall append_call(const char* who, const void* k_new, const void* v_new, in
 }
 int check_append(AppendCall& c) {
   const char* who = c.who;
-  if (!c.k_new.p || !c.v_new.p || !c.k_codes || !c.k_scale || !c.v_cache || !c.k_tail || !c.seqlens || (c.pool.paged && !c.pool.at.block_table))
+  if (!c.k_new.p || !c.v_new.p || !c.k_codes || !c.k_scale || !c.v_cache || !c.k_tail || !c.seqlens || (c.pool.paged && !c.pool.at.block_table) ||
+      (c.v8 && !c.v_scale))
     return fail(LBFA_EINVAL, "%s: null pointer", who);
   if (c.B <= 0 || c.Hkv <= 0 || c.T <= 0) return fail(LBFA_EINVAL, "%s: empty tensor", who);
   if (int st = check_head_dim(c.D, false)) return st;
@@ -999,6 +1010,7 @@ int check_append(AppendCall& c) {
       !aligned(c.seqlens, 4) || !aligned(c.new_lens, 4) || !pool_aligned(c.pool))
     return fail(LBFA_EINVAL, "%s: cache tensors and km must be 16-byte aligned, k_scale / seqlens / new_lens%s 4-byte aligned", who,
                 c.pool.paged ? " / block_table / slots" : "");
+  if (c.v8 && !aligned(c.v_scale, 16)) return fail(LBFA_EINVAL, "%s: v_scale must be 16-byte aligned", who);
   if (c.B > 65535 || c.Hkv > 65535) return fail(LBFA_EINVAL, "%s: grid too large", who);
   return 0;
 }
@@ -1032,6 +1044,9 @@ struct DecodeCall {
   // cached prefill (lbfa_prefill[_paged]): the same call for any Sq, with ragged query lengths
   bool prefill;
   const int32_t* q_lens;
+  // fp8 V cache (the _v8 entry points): v_cache holds e4m3 codes, v_scale one fp32 per key
+  bool v8;
+  const float* v_scale;
 };
 DecodeCall decode_call(const char* who, const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const void* v_cache,
                        const void* km, const int32_t* seqlens, void* o, float* lse, void* workspace, size_t workspace_bytes, int B,
@@ -1047,7 +1062,8 @@ DecodeCall decode_call(const char* who, const void* q, int dtype, const int8_t* 
 }
 int check_decode(DecodeCall& c) {
   const char* who = c.who;
-  if (!c.q.p || !c.o.p || !c.k_codes || !c.k_scale || !c.v_cache || !c.seqlens || (c.pool.paged && !c.pool.at.block_table))
+  if (!c.q.p || !c.o.p || !c.k_codes || !c.k_scale || !c.v_cache || !c.seqlens || (c.pool.paged && !c.pool.at.block_table) ||
+      (c.v8 && !c.v_scale))
     return fail(LBFA_EINVAL, "%s: null pointer", who);
   if (c.B <= 0 || c.Hq <= 0 || c.Hkv <= 0 || c.Sq <= 0) return fail(LBFA_EINVAL, "%s: empty tensor", who);
   if (int st = check_head_dim(c.D, false)) return st;
@@ -1073,6 +1089,7 @@ int check_decode(DecodeCall& c) {
       !pool_aligned(c.pool) || !aligned(c.lse, 4) || !aligned(c.q_lens, 4))
     return fail(LBFA_EINVAL, "%s: cache tensors and km must be 16-byte aligned, k_scale / seqlens%s%s / lse 4-byte aligned", who,
                 c.prefill ? " / q_lens" : "", c.pool.paged ? " / block_table / slots" : "");
+  if (c.v8 && !aligned(c.v_scale, 16)) return fail(LBFA_EINVAL, "%s: v_scale must be 16-byte aligned", who);
   if (c.prefill) c.splits = c.num_splits ? c.num_splits : lbfa_prefill_num_splits(c.B, c.Hq, c.Sq, c.max_seqlen_k);
   else c.splits = c.num_splits ? c.num_splits : lbfa_decode_num_splits(c.B, c.Hkv, c.max_seqlen_k);
   // prefill: grid (Q blocks x slices, Hq, B) of 256 threads, the combine's (M, Hkv, B) of 256: a launch whose gridDim.x * blockDim.x
@@ -1156,6 +1173,42 @@ int lbfa_kvcache_paged_append(const void* k_new, const void* v_new, int dtype, c
   return check_hip(lbfa::launch_kvcache_paged_append(p, dtype, D, (hipStream_t)stream), "lbfa_kvcache_paged_append launch");
 }
 
+// the fp8 V cache: the two appends above with v_cache as e4m3 codes and v_scale, one fp32 per key, behind it
+int lbfa_kvcache_append_v8(const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
+                           int8_t* k_codes, float* k_scale, uint8_t* v_cache, float* v_scale, void* k_tail, const int32_t* seqlens,
+                           int B, int Hkv, int T, int D, int capacity, const int64_t strides_k[3], const int64_t strides_v[3],
+                           int k_qmax, void* stream) {
+  AppendCall c = append_call("lbfa_kvcache_append_v8", k_new, v_new, dtype, new_lens, km, k_codes, k_scale, v_cache, k_tail, seqlens,
+                             B, Hkv, T, D, strides_k, strides_v, k_qmax, Pool{false, capacity, {}});
+  c.v8 = true; c.v_scale = v_scale;
+  if (int st = check_append(c)) return st;
+  lbfa::V8Params<lbfa::AppendParams, float*> p{};
+  fill_append(p, c);
+  p.v_scale = v_scale;
+  g_err[0] = 0;
+  return check_hip(lbfa::launch_kvcache_append_v8(p, dtype, D, (hipStream_t)stream), "lbfa_kvcache_append_v8 launch");
+}
+
+int lbfa_kvcache_paged_append_v8(const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
+                                 int8_t* k_codes, float* k_scale, uint8_t* v_cache, float* v_scale, void* k_tail,
+                                 const int32_t* seqlens, const int32_t* block_table, const int32_t* slots, int B, int Hkv, int T,
+                                 int D, int num_slots, int num_pages, int page_size, int max_pages_per_seq,
+                                 const int64_t strides_k[3], const int64_t strides_v[3], int k_qmax, void* stream) {
+  lbfa::PoolParams at{};
+  at.block_table = block_table; at.slots = slots;
+  at.num_slots = num_slots; at.num_pages = num_pages; at.page_size = page_size; at.max_pages = max_pages_per_seq;
+  AppendCall c = append_call("lbfa_kvcache_paged_append_v8", k_new, v_new, dtype, new_lens, km, k_codes, k_scale, v_cache, k_tail,
+                             seqlens, B, Hkv, T, D, strides_k, strides_v, k_qmax, Pool{true, 0, at});
+  c.v8 = true; c.v_scale = v_scale;
+  if (int st = check_append(c)) return st;
+  lbfa::V8Params<lbfa::PagedAppendParams, float*> p{};
+  fill_append(p, c);
+  static_cast<lbfa::PoolParams&>(p) = c.pool.at;
+  p.v_scale = v_scale;
+  g_err[0] = 0;
+  return check_hip(lbfa::launch_kvcache_paged_append_v8(p, dtype, D, (hipStream_t)stream), "lbfa_kvcache_paged_append_v8 launch");
+}
+
 // The split rule: as many key slices as it takes for B * Hkv * slices one-wave workgroups to reach 1024 (four per CU), but no
 // slice shorter than 4 tiles of 64 keys (below that the per-slice prologue - Q quantiser, first-tile latency - and the
 // partial results outweigh the parallelism), at most 256.  A pure function of its arguments.
@@ -1210,6 +1263,45 @@ int lbfa_decode_paged(const void* q, int dtype, const int8_t* k_codes, const flo
   static_cast<lbfa::PoolParams&>(p) = c.pool.at;
   g_err[0] = 0;
   return check_hip(lbfa::launch_attn_paged_decode(p, dtype, D, (hipStream_t)stream), "lbfa_decode_paged launch");
+}
+
+// the fp8 V cache: the two decodes above with v_cache as e4m3 codes and v_scale, one fp32 per key, behind it
+int lbfa_decode_v8(const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const uint8_t* v_cache, const float* v_scale,
+                   const void* km, const int32_t* seqlens, void* o, float* lse, void* workspace, size_t workspace_bytes,
+                   int B, int Hq, int Hkv, int Sq, int D, int capacity, int max_seqlen_k, int num_splits,
+                   const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream) {
+  DecodeCall c = decode_call("lbfa_decode_v8", q, dtype, k_codes, k_scale, v_cache, km, seqlens, o, lse, workspace, workspace_bytes, B,
+                             Hq, Hkv, Sq, D, max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax, is_causal,
+                             Pool{false, capacity, {}});
+  c.v8 = true; c.v_scale = v_scale;
+  if (int st = check_decode(c)) return st;
+  lbfa::V8Params<lbfa::DecodeParams, const float*> p{};
+  fill_decode(p, c);
+  p.v_scale = v_scale;
+  g_err[0] = 0;
+  return check_hip(lbfa::launch_attn_decode_v8(p, dtype, D, (hipStream_t)stream), "lbfa_decode_v8 launch");
+}
+
+int lbfa_decode_paged_v8(const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const uint8_t* v_cache,
+                         const float* v_scale, const void* km, const int32_t* seqlens, const int32_t* block_table,
+                         const int32_t* slots, void* o, float* lse, void* workspace, size_t workspace_bytes, int B, int Hq, int Hkv,
+                         int Sq, int D, int num_slots, int num_pages, int page_size, int max_pages_per_seq, int max_seqlen_k,
+                         int num_splits, const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax,
+                         int is_causal, void* stream) {
+  lbfa::PoolParams at{};
+  at.block_table = block_table; at.slots = slots;
+  at.num_slots = num_slots; at.num_pages = num_pages; at.page_size = page_size; at.max_pages = max_pages_per_seq;
+  DecodeCall c = decode_call("lbfa_decode_paged_v8", q, dtype, k_codes, k_scale, v_cache, km, seqlens, o, lse, workspace,
+                             workspace_bytes, B, Hq, Hkv, Sq, D, max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax,
+                             is_causal, Pool{true, 0, at});
+  c.v8 = true; c.v_scale = v_scale;
+  if (int st = check_decode(c)) return st;
+  lbfa::V8Params<lbfa::PagedDecodeParams, const float*> p{};
+  fill_decode(p, c);
+  static_cast<lbfa::PoolParams&>(p) = c.pool.at;
+  p.v_scale = v_scale;
+  g_err[0] = 0;
+  return check_hip(lbfa::launch_attn_paged_decode_v8(p, dtype, D, (hipStream_t)stream), "lbfa_decode_paged_v8 launch");
 }
 
 // The split rule of the cached prefill: as many key slices as it takes for B * Hq * ceil(Sq / 128) four-wave workgroups to reach
@@ -1273,6 +1365,49 @@ int lbfa_prefill_paged(const void* q, int dtype, const int8_t* k_codes, const fl
   fill_prefill(p.nQ, p.q_lens, c);
   g_err[0] = 0;
   return check_hip(lbfa::launch_attn_paged_prefill(p, dtype, D, (hipStream_t)stream), "lbfa_prefill_paged launch");
+}
+
+// the fp8 V cache: the two cached prefills above with v_cache as e4m3 codes and v_scale, one fp32 per key, behind it
+int lbfa_prefill_v8(const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const uint8_t* v_cache, const float* v_scale,
+                    const void* km, const int32_t* seqlens, const int32_t* q_lens, void* o, float* lse, void* workspace,
+                    size_t workspace_bytes, int B, int Hq, int Hkv, int Sq, int D, int capacity, int max_seqlen_k, int num_splits,
+                    const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream) {
+  DecodeCall c = decode_call("lbfa_prefill_v8", q, dtype, k_codes, k_scale, v_cache, km, seqlens, o, lse, workspace, workspace_bytes,
+                             B, Hq, Hkv, Sq, D, max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax, is_causal,
+                             Pool{false, capacity, {}});
+  c.prefill = true; c.q_lens = q_lens;
+  c.v8 = true; c.v_scale = v_scale;
+  if (int st = check_decode(c)) return st;
+  lbfa::V8Params<lbfa::PrefillParams, const float*> p{};
+  fill_decode(p, c);
+  fill_prefill(p.nQ, p.q_lens, c);
+  p.v_scale = v_scale;
+  g_err[0] = 0;
+  return check_hip(lbfa::launch_attn_prefill_v8(p, dtype, D, (hipStream_t)stream), "lbfa_prefill_v8 launch");
+}
+
+int lbfa_prefill_paged_v8(const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const uint8_t* v_cache,
+                          const float* v_scale, const void* km, const int32_t* seqlens, const int32_t* q_lens,
+                          const int32_t* block_table, const int32_t* slots, void* o, float* lse, void* workspace,
+                          size_t workspace_bytes, int B, int Hq, int Hkv, int Sq, int D, int num_slots, int num_pages, int page_size,
+                          int max_pages_per_seq, int max_seqlen_k, int num_splits, const int64_t strides_q[3],
+                          const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream) {
+  lbfa::PoolParams at{};
+  at.block_table = block_table; at.slots = slots;
+  at.num_slots = num_slots; at.num_pages = num_pages; at.page_size = page_size; at.max_pages = max_pages_per_seq;
+  DecodeCall c = decode_call("lbfa_prefill_paged_v8", q, dtype, k_codes, k_scale, v_cache, km, seqlens, o, lse, workspace,
+                             workspace_bytes, B, Hq, Hkv, Sq, D, max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax,
+                             is_causal, Pool{true, 0, at});
+  c.prefill = true; c.q_lens = q_lens;
+  c.v8 = true; c.v_scale = v_scale;
+  if (int st = check_decode(c)) return st;
+  lbfa::V8Params<lbfa::PagedPrefillParams, const float*> p{};
+  fill_decode(p, c);
+  static_cast<lbfa::PoolParams&>(p) = c.pool.at;
+  fill_prefill(p.nQ, p.q_lens, c);
+  p.v_scale = v_scale;
+  g_err[0] = 0;
+  return check_hip(lbfa::launch_attn_paged_prefill_v8(p, dtype, D, (hipStream_t)stream), "lbfa_prefill_paged_v8 launch");
 }
 
 }  // extern "C"

@@ -322,4 +322,14 @@ struct PagedPrefillParams : PagedDecodeParams {
   int nQ;
 };
 
+
+// The fp8 V cache (v_bits = 8): `v` of the block points at e4m3fn codes, one byte per element in the layout of the fp16 V, and
+// v_scale holds one fp32 per key and kv head - [B, Hkv, cap], paged [num_pages, Hkv, page_size] - found from the same tile number
+// as the codes.  The parameter block of an fp8-V instance is its fp16 sibling's with the scales behind it (float* for the append,
+// const float* for the readers); only the *_v8_kernel instances see the field.
+template <class Base, class ScalePtr>
+struct V8Params : Base {
+  ScalePtr v_scale;
+};
+
 }  // namespace lbfa

@@ -13,9 +13,17 @@ and every sequence has a smooth-K mean of its own.  State and decode results equ
 a long prompt, the next turn over a cached prefix, a verify step of more than 64 rows.  Q is quantised in the kernel in the dense
 operators' 128-row blocks, the causal mask is bottom-right aligned, query and key lengths are ragged device tensors.
 
-Not here: prefix sharing / copy-on-write between sequences, an fp8 V cache and fp8 PV over the cache (the per-channel scale needs
-the whole sequence), nibble-packed int4 (the +-7 codes take a byte each), a backward through the cache, Paddle tensors, routing
-`lowbit_fa_decode` calls with more than 64 rows to the prefill kernel (decode keeps refusing them).
+`v_bits=8` (either cache; the default 16 changes nothing) keeps V as OCP e4m3fn codes with ONE fp32 scale per key and kv head
+(`lbfa_*_v8`): the decode kernel then streams 2 D + 4 bytes per key instead of 3 D and the cache takes about two thirds of the
+memory.  The quantiser of an appended row works on its Dp channels in fp32: `amax = max(max |x|, 1e-7)`, `scale = amax / 448`,
+`code = e4m3fn_rne(x / scale)`; a row is written once and never re-quantised, so any append schedule gives the state of a one-shot
+append bit for bit, and the K state is exactly that of a `v_bits=16` cache.  A reader sees `V^ = fp16_rne(fp32(decode(code)) *
+scale)` (`dequantized_v()`), with `|V^ - V| <= (2^-4 + 2^-10) |V| + 2^-10 scale + 2^-24` per element, and a read equals, bit for
+bit, the same read of a `v_bits=16` cache whose `v` holds V^.  `k_bits` and `v_bits` are independent.
+
+Not here: prefix sharing / copy-on-write between sequences, fp8 P or an fp8 MFMA over the cache (V^ enters the fp16 MFMA), nibble-
+packed int4 (the +-7 codes take a byte each), a backward through the cache, Paddle tensors, routing `lowbit_fa_decode` calls with
+more than 64 rows to the prefill kernel (decode keeps refusing them).
 """
 from __future__ import annotations
 
@@ -58,6 +66,18 @@ def _append_operands(cache, k, v, tensor_layout: str):
     return ops, k, v, bht, k3, v3
 
 
+def _check_v_bits(v_bits: int) -> int:
+    if v_bits not in (16, 8):
+        raise ValueError(f"v_bits must be 16 or 8, got {v_bits}")
+    return int(v_bits)
+
+
+def _dequant_v(v, v_scale):
+    """V^ of an fp8 V cache: fp16_rne(fp32(e4m3 code) * scale), what the kernels read"""
+    import torch
+    return (v.view(torch.float8_e4m3fn).float() * v_scale[..., None]).to(torch.float16)
+
+
 def _new_lens_i32(cache, ops, new_lens, n: int, per: str):
     """new_lens of an append of n rows as an int32 tensor on the cache's device (None stays None)"""
     if new_lens is not None:
@@ -87,13 +107,18 @@ class LowbitKVCache:
     State (all on `device`): k_codes int8 [B, Hkv, cap, Dp], k_scale fp32 [B, Hkv, cap / 64], v fp16 [B, Hkv, cap, Dp],
     k_tail [B, Hkv, 64, Dp] (raw rows of the open 64-key block), km [B, Hkv, Dp] or None, seqlens int32 [B]; Dp = head_dim
     zero-padded to 64 / 128.  `km`, the smooth-K mean, is taken from the FIRST append and fixed from then on.
+    With `v_bits=8`, v is uint8 [B, Hkv, cap, Dp] (e4m3fn bit patterns) and v_scale fp32 [B, Hkv, cap] holds the scale of each row
+    (module docstring); with the default 16 there is no v_scale.
     No host read of `seqlens` happens anywhere: the host only tracks an upper bound of the lengths (the rows offered so far)."""
 
+    v_bits = 16  # bits of a cached V element; 8 adds `v_scale`
+
     def __init__(self, batch: int, num_kv_heads: int, head_dim: int, capacity: int, dtype, device, k_bits: int = 8,
-                 smooth_k: bool = True):
+                 smooth_k: bool = True, v_bits: int = 16):
         import torch
         if k_bits not in (8, 4):
             raise ValueError(f"k_bits must be 8 or 4, got {k_bits}")
+        self.v_bits = _check_v_bits(v_bits)
         if dtype not in (torch.float16, torch.bfloat16):
             raise ValueError("dtype must be torch.float16 or torch.bfloat16")
         if batch <= 0 or num_kv_heads <= 0 or capacity <= 0:
@@ -109,7 +134,11 @@ class LowbitKVCache:
         B, H, C, D = self.batch, self.num_kv_heads, self.capacity, self.padded_head_dim
         self.k_codes = torch.zeros((B, H, C, D), dtype=torch.int8, device=self.device)
         self.k_scale = torch.zeros((B, H, C // _lib.BLKK), dtype=torch.float32, device=self.device)
-        self.v = torch.zeros((B, H, C, D), dtype=torch.float16, device=self.device)
+        if self.v_bits == 8:
+            self.v = torch.zeros((B, H, C, D), dtype=torch.uint8, device=self.device)
+            self.v_scale = torch.zeros((B, H, C), dtype=torch.float32, device=self.device)
+        else:
+            self.v = torch.zeros((B, H, C, D), dtype=torch.float16, device=self.device)
         self.k_tail = torch.zeros((B, H, _lib.BLKK, D), dtype=dtype, device=self.device)
         self.km = torch.zeros((B, H, D), dtype=dtype, device=self.device) if self.smooth_k else None
         self.seqlens = torch.zeros((B,), dtype=torch.int32, device=self.device)
@@ -135,11 +164,13 @@ class LowbitKVCache:
             if self.smooth_k and not self._has_km:
                 _first_append_mean(lib, ops, k, k3, new_lens, self.km, B, H, T, D, stream)
                 self._has_km = True
-            _lib.check(lib.lbfa_kvcache_append(k.data_ptr(), v.data_ptr(), code, new_lens.data_ptr() if new_lens is not None else None,
-                                               self.km.data_ptr() if self.smooth_k else None, self.k_codes.data_ptr(),
-                                               self.k_scale.data_ptr(), self.v.data_ptr(), self.k_tail.data_ptr(),
-                                               self.seqlens.data_ptr(), B, H, T, D, self.capacity, _lib.strides3(k3),
-                                               _lib.strides3(v3), self.k_qmax, stream), lib)
+            v8 = self.v_bits == 8  # the _v8 entry point takes v_scale behind v_cache
+            entry = lib.lbfa_kvcache_append_v8 if v8 else lib.lbfa_kvcache_append
+            _lib.check(entry(k.data_ptr(), v.data_ptr(), code, new_lens.data_ptr() if new_lens is not None else None,
+                             self.km.data_ptr() if self.smooth_k else None, self.k_codes.data_ptr(), self.k_scale.data_ptr(),
+                             self.v.data_ptr(), *((self.v_scale.data_ptr(),) if v8 else ()), self.k_tail.data_ptr(),
+                             self.seqlens.data_ptr(), B, H, T, D, self.capacity, _lib.strides3(k3), _lib.strides3(v3), self.k_qmax,
+                             stream), lib)
             # the kernel reads seqlens and does not advance it
             if new_lens is None:
                 self.seqlens += T
@@ -155,6 +186,12 @@ class LowbitKVCache:
         if self.km is not None:
             k = k + self.km.float()[:, :, None, :]
         return k[..., :self.head_dim]
+
+    def dequantized_v(self):
+        """Debugging aid (torch ops, read-only): fp16 [B, Hkv, capacity, head_dim], the V the kernels read - with `v_bits=8`
+        V^ = fp16(fp32(code) * scale), else `v` itself.  Rows at or past seqlens[b] are meaningless."""
+        v = _dequant_v(self.v, self.v_scale) if self.v_bits == 8 else self.v
+        return v[..., :self.head_dim]
 
 
 class PageAllocator:
@@ -235,15 +272,20 @@ class LowbitPagedKVCache:
     State (public, all on `device`; the layout `lbfa_kvcache_paged_append` / `lbfa_decode_paged` take): k_codes int8
     [num_pages, Hkv, page_size, Dp], k_scale fp32 [num_pages, Hkv, page_size / 64], v fp16 [num_pages, Hkv, page_size, Dp],
     block_table int32 [max_seqs, max_pages_per_seq], k_tail [max_seqs, Hkv, 64, Dp], km [max_seqs, Hkv, Dp] or None, seqlens int32
-    [max_seqs].  `allocator` (a `PageAllocator`) is the host side.  `km` is PER SEQUENCE: a slot that holds nothing is fresh, and
+    [max_seqs].  With `v_bits=8`, v is uint8 [num_pages, Hkv, page_size, Dp] (e4m3fn bit patterns) and v_scale fp32 [num_pages, Hkv,
+    page_size] holds the scale of each row, addressed by the same page and row as the codes.  `allocator` (a `PageAllocator`) is the host side.  `km` is PER SEQUENCE: a slot that holds nothing is fresh, and
     takes its mean from its first append.  As in `LowbitKVCache` no host read of device lengths happens anywhere: pages are
     allocated for the upper bound of each length."""
 
+    v_bits = 16  # bits of a cached V element; 8 adds `v_scale`
+
     def __init__(self, num_pages: int, page_size: int, num_kv_heads: int, head_dim: int, max_seqs: int, max_pages_per_seq: int,
-                 dtype, device, k_bits: int = 8, smooth_k: bool = True, page_order: Optional[Iterable[int]] = None):
+                 dtype, device, k_bits: int = 8, smooth_k: bool = True, page_order: Optional[Iterable[int]] = None,
+                 v_bits: int = 16):
         import torch
         if k_bits not in (8, 4):
             raise ValueError(f"k_bits must be 8 or 4, got {k_bits}")
+        self.v_bits = _check_v_bits(v_bits)
         if dtype not in (torch.float16, torch.bfloat16):
             raise ValueError("dtype must be torch.float16 or torch.bfloat16")
         if num_kv_heads <= 0:
@@ -261,7 +303,11 @@ class LowbitPagedKVCache:
         N, S, H, P, D = self.num_pages, self.max_seqs, self.num_kv_heads, self.page_size, self.padded_head_dim
         self.k_codes = torch.zeros((N, H, P, D), dtype=torch.int8, device=self.device)
         self.k_scale = torch.zeros((N, H, P // _lib.BLKK), dtype=torch.float32, device=self.device)
-        self.v = torch.zeros((N, H, P, D), dtype=torch.float16, device=self.device)
+        if self.v_bits == 8:
+            self.v = torch.zeros((N, H, P, D), dtype=torch.uint8, device=self.device)
+            self.v_scale = torch.zeros((N, H, P), dtype=torch.float32, device=self.device)
+        else:
+            self.v = torch.zeros((N, H, P, D), dtype=torch.float16, device=self.device)
         self.block_table = torch.zeros((S, self.max_pages_per_seq), dtype=torch.int32, device=self.device)
         self.k_tail = torch.zeros((S, H, _lib.BLKK, D), dtype=dtype, device=self.device)
         self.km = torch.zeros((S, H, D), dtype=dtype, device=self.device) if self.smooth_k else None
@@ -301,9 +347,12 @@ class LowbitPagedKVCache:
                 _first_append_mean(lib, ops, k, k3, new_lens, km_new, n, H, T, D, stream)
                 rows = torch.tensor(fresh, dtype=torch.int64, device=self.device)
                 self.km.index_copy_(0, torch.tensor([slots[i] for i in fresh], dtype=torch.int64, device=self.device), km_new[rows])
-            _lib.check(lib.lbfa_kvcache_paged_append(
+            v8 = self.v_bits == 8  # the _v8 entry point takes v_scale behind v_cache
+            entry = lib.lbfa_kvcache_paged_append_v8 if v8 else lib.lbfa_kvcache_paged_append
+            _lib.check(entry(
                 k.data_ptr(), v.data_ptr(), code, new_lens.data_ptr() if new_lens is not None else None,
                 self.km.data_ptr() if self.smooth_k else None, self.k_codes.data_ptr(), self.k_scale.data_ptr(), self.v.data_ptr(),
+                *((self.v_scale.data_ptr(),) if v8 else ()),
                 self.k_tail.data_ptr(), self.seqlens.data_ptr(), self.block_table.data_ptr(),
                 slot_t.data_ptr() if slot_t is not None else None, n, H, T, D, self.max_seqs, self.num_pages, self.page_size,
                 self.max_pages_per_seq, _lib.strides3(k3), _lib.strides3(v3), self.k_qmax, stream), lib)
@@ -332,15 +381,24 @@ class LowbitPagedKVCache:
 
     def gather(self, slot: int):
         """Debugging aid (torch ops, read-only): the sequence in `slot` through its block table as contiguous tensors - codes
-        int8 [Hkv, n, Dp], scales fp32 [Hkv, n / 64], V fp16 [Hkv, n, Dp], n = its pages * page_size.  Rows at or past
-        seqlens[slot] are meaningless."""
+        int8 [Hkv, n, Dp], scales fp32 [Hkv, n / 64], V fp16 [Hkv, n, Dp], n = its pages * page_size; with `v_bits=8` V is the
+        uint8 codes and a fourth tensor follows, their scales fp32 [Hkv, n].  Rows at or past seqlens[slot] are meaningless."""
         import torch
         idx = torch.tensor(self.allocator.pages[slot], dtype=torch.int64, device=self.device)
         H, D = self.num_kv_heads, self.padded_head_dim
         # (contiguous() : with one 64-key block per page the reshape of the scales is a strided view)
-        return (self.k_codes[idx].transpose(0, 1).reshape(H, -1, D).contiguous(),
-                self.k_scale[idx].transpose(0, 1).reshape(H, -1).contiguous(),
-                self.v[idx].transpose(0, 1).reshape(H, -1, D).contiguous())
+        out = (self.k_codes[idx].transpose(0, 1).reshape(H, -1, D).contiguous(),
+               self.k_scale[idx].transpose(0, 1).reshape(H, -1).contiguous(),
+               self.v[idx].transpose(0, 1).reshape(H, -1, D).contiguous())
+        if self.v_bits == 8:
+            out += (self.v_scale[idx].transpose(0, 1).reshape(H, -1).contiguous(),)
+        return out
+
+    def dequantized_v(self):
+        """Debugging aid (torch ops, read-only): fp16 [num_pages, Hkv, page_size, head_dim], the V the kernels read - with
+        `v_bits=8` V^ = fp16(fp32(code) * scale), else `v` itself.  Rows no sequence holds are meaningless."""
+        v = _dequant_v(self.v, self.v_scale) if self.v_bits == 8 else self.v
+        return v[..., :self.head_dim]
 
 
 def _attend(who: str, q, cache, tensor_layout, is_causal, sm_scale, return_lse, num_splits, q_bits, slots, q_lens, prefill: bool):
@@ -405,7 +463,11 @@ def _attend(who: str, q, cache, tensor_layout, is_causal, sm_scale, return_lse, 
         #   lbfa_decode:        head (q .. seqlens), out (o .. D), capacity, rest (max_seqlen_k .. stream)
         #   lbfa_decode_paged:  head, block_table, slots, out, num_slots .. max_pages_per_seq, rest
         #   lbfa_prefill[_paged]: the same with q_lens behind seqlens
+        #   the _v8 forms: the same with v_scale behind v_cache
+        # an fp8 V cache: the _v8 entry points, v_scale behind v_cache
+        v8 = cache.v_bits == 8
         head = (q.data_ptr(), ops.dtype_code(q), cache.k_codes.data_ptr(), cache.k_scale.data_ptr(), cache.v.data_ptr(),
+                *((cache.v_scale.data_ptr(),) if v8 else ()),
                 cache.km.data_ptr() if cache.km is not None else None, cache.seqlens.data_ptr())
         if prefill:
             head += (q_lens.data_ptr() if q_lens is not None else None,)
@@ -414,11 +476,11 @@ def _attend(who: str, q, cache, tensor_layout, is_causal, sm_scale, return_lse, 
                 1 if is_causal else 0, ops.stream(q))
         if paged:
             slot_t = torch.tensor(slot_list, dtype=torch.int32, device=cache.device) if slots is not None else None
-            entry = lib.lbfa_prefill_paged if prefill else lib.lbfa_decode_paged
+            entry = getattr(lib, ("lbfa_prefill_paged" if prefill else "lbfa_decode_paged") + ("_v8" if v8 else ""))
             status = entry(*head, cache.block_table.data_ptr(), slot_t.data_ptr() if slot_t is not None else None,
                            *out, cache.max_seqs, cache.num_pages, cache.page_size, cache.max_pages_per_seq, *rest)
         else:
-            entry = lib.lbfa_prefill if prefill else lib.lbfa_decode
+            entry = getattr(lib, ("lbfa_prefill" if prefill else "lbfa_decode") + ("_v8" if v8 else ""))
             status = entry(*head, *out, cache.capacity, *rest)
         _lib.check(status, lib)
     o = o[..., :head_dim_og]

@@ -10,6 +10,9 @@ Shapes: Hq 32 / Hkv 8, D 128, Sq 1, B in {1, 8, 64} x context in {4K, 32K, 128K}
   decode_paged      `lowbit_fa_decode` on a `LowbitPagedKVCache` holding the same keys in pages of 64 handed out in a RANDOM order:
                     the worst case, one table look-up per tile and no locality between tiles
   decode_paged_256  the same with pages of 256 keys
+  decode_v8         `lowbit_fa_decode` on a `LowbitKVCache(..., v_bits=8)` holding the same keys: V as e4m3 codes with one fp32
+                    scale per key, 2 D + 4 bytes per key and kv head instead of 3 D
+  decode_v8_paged_256  the same on a `LowbitPagedKVCache(..., v_bits=8)` with pages of 256 keys in a random order
   dense_int8   the dense int8 operator at Sq = 1 on the 16-bit K / V (`lowbit_fa_qk_int8_pv_fp16_triton`): what the library offered
                for a decode step before the cache existed - it re-smooths and re-quantises K on every call
   sdpa_fp16    torch's scaled_dot_product_attention on the fp16 K / V, the Hq / Hkv query heads of a kv head as its query rows
@@ -20,10 +23,14 @@ Prints one JSON document (and writes it to --out).
 
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/bench_decode.py --calls-only [--shapes ...]
 
-`--calls-only` fills the caches and makes ten calls of `decode`, `decode_1` and `decode_paged` per shape, untimed: the run to put
+`--calls-only` fills the caches and makes ten calls of `decode`, `decode_1`, `decode_paged` and `decode_v8` per shape, untimed: the run to put
 under the profiler for per-kernel times (profiles/decode_kernel_trace.json), separate from the timed run.
 The yardstick of the paged arms is the `decode` arm of the same run: `decode_paged*_vs_decode` is the ratio of the medians and
 `decode_paged*_within_decode_p10_p90` says whether the paged median lies inside the contiguous arm's 10th .. 90th percentile band.
+The fp8-V arms are measured against it too: `decode_v8*_speedup_vs_decode` is decode's median over theirs (its ceiling, from the
+bytes alone, is 3 D / (2 D + 4)), `decode_v8*_median_below_decode_p10` says whether the median lies below the 10th percentile of
+the `decode` arm, each has its share of the HBM ceiling under its own traffic model, and `decode_v8_vs_decode_output` is what the
+format costs in accuracy: max |dO| and the mean squared difference of the `decode_v8` output against the `decode` output.
 """
 import argparse
 import json
@@ -47,14 +54,15 @@ def _pct(xs, p):
     return xs[min(len(xs) - 1, int(round(p * (len(xs) - 1))))]
 
 
-def _paged_cache(lb, k, v, page, seed):
+def _paged_cache(lb, k, v, page, seed, v_bits=16):
     """the keys of k, v in a paged cache whose pages are handed out in a random order"""
     B, S = k.shape[0], k.shape[2]
     per_seq = (S + page - 1) // page
     g = torch.Generator()
     g.manual_seed(seed)
     order = torch.randperm(B * per_seq, generator=g).tolist()
-    return lb.LowbitPagedKVCache(B * per_seq, page, HKV, D, B, per_seq, torch.float16, k.device, page_order=order).append(k, v)
+    return lb.LowbitPagedKVCache(B * per_seq, page, HKV, D, B, per_seq, torch.float16, k.device, page_order=order,
+                                 v_bits=v_bits).append(k, v)
 
 
 def run_shape(name, B, S, steps, warmup):
@@ -67,19 +75,26 @@ def run_shape(name, B, S, steps, warmup):
     q = torch.randn((B, HQ, 1, D), device=dev, dtype=torch.float16)
     cache = lb.LowbitKVCache(B, HKV, D, S, torch.float16, dev).append(k, v)
     paged64, paged256 = _paged_cache(lb, k, v, 64, 1), _paged_cache(lb, k, v, 256, 2)
+    cache8 = lb.LowbitKVCache(B, HKV, D, S, torch.float16, dev, v_bits=8).append(k, v)
+    paged256_8 = _paged_cache(lb, k, v, 256, 2, v_bits=8)
     q_rows = q.view(B, HKV, HQ // HKV, D)  # the query heads of a kv head as query rows of one head
     arms = {
         "decode": lambda: lb.lowbit_fa_decode(q, cache),
         "decode_1": lambda: lb.lowbit_fa_decode(q, cache, num_splits=1),
         "decode_paged": lambda: lb.lowbit_fa_decode(q, paged64),
         "decode_paged_256": lambda: lb.lowbit_fa_decode(q, paged256),
+        "decode_v8": lambda: lb.lowbit_fa_decode(q, cache8),
+        "decode_v8_paged_256": lambda: lb.lowbit_fa_decode(q, paged256_8),
         "dense_int8": lambda: lb.lowbit_fa_qk_int8_pv_fp16_triton(q, k, v),
         "sdpa_fp16": lambda: F.scaled_dot_product_attention(q_rows, k, v),
     }
     with torch.no_grad():
         ref = arms["sdpa_fp16"]().view(B, HQ, 1, D).float()
-        err = {a: float((arms[a]().float() - ref).abs().max()) for a in ("decode", "decode_1", "dense_int8")}
+        err = {a: float((arms[a]().float() - ref).abs().max()) for a in ("decode", "decode_1", "dense_int8", "decode_v8")}
         same = {a: bool(torch.equal(arms[a](), arms["decode"]())) for a in ("decode_paged", "decode_paged_256")}
+        same["decode_v8_paged_256_to_decode_v8"] = bool(torch.equal(arms["decode_v8_paged_256"](), arms["decode_v8"]()))
+        d8 = arms["decode_v8"]().float() - arms["decode"]().float()
+        v8_cost = dict(max_abs=float(d8.abs().max()), mse=float((d8 * d8).mean()), rms_of_decode_output=float(arms["decode"]().float().pow(2).mean().sqrt()))
         for _ in range(warmup):
             for fn in arms.values():
                 fn()
@@ -94,8 +109,10 @@ def run_shape(name, B, S, steps, warmup):
                 ts[a].append(e0.elapsed_time(e1) * 1e3)
     splits = _lib.load().lbfa_decode_num_splits(B, HKV, S)
     bytes_needed = B * HKV * (S * 3 * D + (S // 64) * 4) + 2 * B * HQ * D * 2
+    bytes_needed_v8 = B * HKV * (S * (2 * D + 4) + (S // 64) * 4) + 2 * B * HQ * D * 2  # D code bytes + D e4m3 bytes + a scale per key
     rec = dict(shape=name, B=B, Hq=HQ, Hkv=HKV, Sq=1, context=S, D=D, num_splits=splits, bytes_needed=bytes_needed,
-               max_abs_diff_vs_sdpa=err, paged_bit_identical_to_decode=same)
+               bytes_needed_v8=bytes_needed_v8, max_abs_diff_vs_sdpa=err, paged_bit_identical_to_decode=same,
+               decode_v8_vs_decode_output=v8_cost)
     for a in arms:
         rec[a + "_us"] = statistics.median(ts[a])
         rec[a + "_us_p10_p90"] = [_pct(ts[a], 0.1), _pct(ts[a], 0.9)]
@@ -107,6 +124,11 @@ def run_shape(name, B, S, steps, warmup):
         rec[f"{a}_vs_decode"] = rec[a + "_us"] / rec["decode_us"]
         rec[f"{a}_within_decode_p10_p90"] = lo <= rec[a + "_us"] <= hi
         rec[f"{a}_slower_beyond_spread"] = rec[a + "_us_p10_p90"][0] > hi
+    rec["decode_v8_speedup_ceiling"] = 3 * D / (2 * D + 4)
+    for a in ("decode_v8", "decode_v8_paged_256"):
+        rec[f"{a}_share_of_hbm_ceiling"] = bytes_needed_v8 / (rec[a + "_us"] * 1e-6) / HBM_CEILING
+        rec[f"{a}_speedup_vs_decode"] = rec["decode_us"] / rec[a + "_us"]
+        rec[f"{a}_median_below_decode_p10"] = rec[a + "_us"] < lo
     # faster than the dense operator by more than the run-to-run spread: its fastest decile against our slowest
     rec["beats_dense_int8_beyond_spread"] = rec["dense_int8_us_p10_p90"][0] > rec["decode_us_p10_p90"][1]
     return rec
@@ -121,10 +143,12 @@ def calls_only(B, S, calls=10):
     q = torch.randn((B, HQ, 1, D), device=dev, dtype=torch.float16)
     cache = lb.LowbitKVCache(B, HKV, D, S, torch.float16, dev).append(k, v)
     paged = _paged_cache(lb, k, v, 64, 1)
+    cache8 = lb.LowbitKVCache(B, HKV, D, S, torch.float16, dev, v_bits=8).append(k, v)
     for _ in range(calls):
         lb.lowbit_fa_decode(q, cache)
         lb.lowbit_fa_decode(q, cache, num_splits=1)
         lb.lowbit_fa_decode(q, paged)
+        lb.lowbit_fa_decode(q, cache8)
     torch.cuda.synchronize()
 
 

@@ -10,6 +10,9 @@ alternated step by step in one process (so drift hits all alike), each step brac
 percentile per arm:
   prefill        `lowbit_fa_prefill` on a filled `LowbitKVCache`, num_splits chosen by lbfa_prefill_num_splits
   prefill_1      the same with one key slice: decides whether the starting split rule stays
+  prefill_v8     `lowbit_fa_prefill` on a `LowbitKVCache(..., v_bits=8)` holding the same keys (V as e4m3 codes with a scale per
+                 key), the chosen num_splits.  Prefill is not bound by the stream: the arm only has to be no slower than `prefill` -
+                 `prefill_v8_over_prefill` is the ratio of the medians, `prefill_v8_not_above_prefill_p90` the verdict
   dense_int8     the dense int8 operator on the 16-bit K, V at the same Sq x Sk, NON-causal (its causal mask needs Sq == Sk) - all a
                  user could do before; it takes the mean, quantises and re-reads the whole context on every call
   dense_causal   the dense int8 operator, causal, where Sq == Sk
@@ -23,7 +26,7 @@ Every arm is CHECKED before it is timed (`oracle_check`): the numpy oracle is to
 at a reduced shape of the same kind - B 1, Hq 8 / Hkv 2 (the same G), the same D, mask and num_splits, Sq cut to 256 and the
 context to 1024 keys (Sq = n stays Sq = n) - and every element of its output is held to the operator bound
 |dO| <= 2e-3 + 2e-3 |O| (tests/kvcache_reference.py `o_bound`) of ITS oracle on those inputs: `oracle_prefill` on a numpy cache
-for the prefill arms, `oracle_decode` per 64-row piece for the decode loop, the dense oracle (`lowbit_fa_forward`) for the dense
+for the prefill arms (`prefill_v8`: on the numpy cache's codes and V^, tests/v8_reference.py), `oracle_decode` per 64-row piece for the decode loop, the dense oracle (`lowbit_fa_forward`) for the dense
 arms, fp32 attention for fp16 SDPA.  A ratio above 1 ends the run with an error; the ratios go into the JSON
 (`oracle_check`).  `max_abs_diff_vs_fp32_attention_last_rows` is a figure at the timed size, beside the check.
 Prints one JSON document (and writes it to --out).
@@ -92,7 +95,7 @@ def _reference_rows(q, k, v, rows, n, Sq, causal):
     return torch.einsum("bhgqk,bhkd->bhgqd", torch.softmax(s, dim=-1), v.float()).reshape(q.shape[0], HQ, -1, q.shape[-1])
 
 
-def make_arms(lb, q, k, v, cache, causal, splits, with_sdpa):
+def make_arms(lb, q, k, v, cache, causal, splits, with_sdpa, cache8=None):
     """name -> call, for inputs of any size: the timed arms and their reduced twins of `oracle_check` are built here alike"""
     Sq, n, dev = q.shape[2], k.shape[2], q.device
     arms = {
@@ -100,6 +103,8 @@ def make_arms(lb, q, k, v, cache, causal, splits, with_sdpa):
         "prefill_1": lambda: lb.lowbit_fa_prefill(q, cache, is_causal=causal, num_splits=1),
         "dense_int8": lambda: lb.lowbit_fa_qk_int8_pv_fp16_triton(q, k, v),
     }
+    if cache8 is not None:
+        arms["prefill_v8"] = lambda: lb.lowbit_fa_prefill(q, cache8, is_causal=causal, num_splits=splits)
     if causal and Sq == n:
         arms["dense_causal"] = lambda: lb.lowbit_fa_qk_int8_pv_fp16_triton(q, k, v, is_causal=True)
     if with_sdpa:
@@ -120,8 +125,11 @@ def _oracle_references(D, Sq, n, causal):
     """the reduced problem (B 1, Hq 8 / Hkv 2) and the oracle output of every kind of arm on it, computed once per shape"""
     import numpy as np
 
+    import types
+
     import kvcache_reference as kr
     import prefill_reference as pr
+    import v8_reference as v8
     from oracle import lowbit_fa_oracle as orc
     key = (D, Sq, n, causal)
     if key in _oracle_refs:
@@ -130,11 +138,13 @@ def _oracle_references(D, Sq, n, causal):
     rng = np.random.default_rng(1000 * D + Sq + n)
     mk = lambda h, rows: orc.to_storage(rng.standard_normal((1, h, rows, D), dtype=np.float32), "fp16")
     q, k, v = mk(hq, Sq), mk(hkv, n), mk(hkv, n)
-    ref = kr.CacheRef(orc, 1, hkv, D, (n + 63) // 64 * 64, "fp16")
+    ref = v8.CacheRefV8(orc, 1, hkv, D, (n + 63) // 64 * 64, "fp16")  # the K state and the fp16 V are CacheRef's
     ref.append(k, v)
     q_i8, q_scale = pr.quant_q_blocks(orc, q, [Sq], sm, 127)
     want = {"prefill": pr.oracle_prefill(orc, q_i8, q_scale, ref, [Sq], causal=causal, out_dtype="fp16")[0]}
     want["prefill_1"] = want["prefill"]
+    ref_hat = types.SimpleNamespace(k_codes=ref.k_codes, k_scale=ref.k_scale, v=ref.vhat(), seqlens=ref.seqlens)
+    want["prefill_v8"] = pr.oracle_prefill(orc, q_i8, q_scale, ref_hat, [Sq], causal=causal, out_dtype="fp16")[0]
     want["dense_int8"] = orc.lowbit_fa_forward(q, k, v, is_causal=False, tail="neg_inf", amax_floor=1e-7)
     if causal and Sq == n:
         want["dense_causal"] = orc.lowbit_fa_forward(q, k, v, is_causal=True, tail="neg_inf", amax_floor=1e-7)
@@ -164,9 +174,10 @@ def oracle_check(lb, name, Sq, n, D, causal, splits):
     tq, tk, tv = (torch.from_numpy(a).to(torch.float16).to(dev) for a in (q, k, v))
     # (new_lens given: the mean of the first append is then taken as the numpy cache takes it, over the valid rows in float64)
     cache = lb.LowbitKVCache(1, 2, D, n_r, torch.float16, dev).append(tk, tv, new_lens=torch.full((1,), n_r, dtype=torch.int32))
+    cache8 = lb.LowbitKVCache(1, 2, D, n_r, torch.float16, dev, v_bits=8).append(tk, tv, new_lens=torch.full((1,), n_r, dtype=torch.int32))
     ratios = {}
     with torch.no_grad():
-        for a, fn in make_arms(lb, tq, tk, tv, cache, causal, splits, True).items():
+        for a, fn in make_arms(lb, tq, tk, tv, cache, causal, splits, True, cache8).items():
             got = fn().float().cpu().numpy().astype("float64")
             err = abs(got - want[a])
             ratios[a] = float((err / kr.o_bound(want[a], "fp16")).max())
@@ -185,7 +196,8 @@ def run_shape(name, B, Sq, n, D, causal, steps, warmup):
     checked_by_oracle = oracle_check(lb, name, Sq, n, D, causal, splits)
     q, k, v = _inputs(B, Sq, n, D, dev)
     cache = lb.LowbitKVCache(B, HKV, D, n, torch.float16, dev).append(k, v)
-    arms = make_arms(lb, q, k, v, cache, causal, 0, B * HQ * Sq * n <= SDPA_MAX_SCORES)
+    cache8 = lb.LowbitKVCache(B, HKV, D, n, torch.float16, dev, v_bits=8).append(k, v)
+    arms = make_arms(lb, q, k, v, cache, causal, 0, B * HQ * Sq * n <= SDPA_MAX_SCORES, cache8)
     with torch.no_grad():
         rows = slice(max(0, Sq - 64), Sq)  # the last rows see the most keys
         ref = _reference_rows(q, k, v, rows, n, Sq, causal)
@@ -216,6 +228,10 @@ def run_shape(name, B, Sq, n, D, causal, steps, warmup):
         rec[a + "_share_of_mixed_roof"] = rec[a + "_tflops"] / PEAK_MIX_TF
         rec[a + "_share_of_hbm_ceiling_one_pass"] = stream_bytes / (rec[a + "_us"] * 1e-6) / HBM_CEILING
     rec["chosen_vs_one_slice"] = rec["prefill_us"] / rec["prefill_1_us"]
+    rec["prefill_v8_over_prefill"] = rec["prefill_v8_us"] / rec["prefill_us"]
+    rec["prefill_v8_not_above_prefill_p90"] = rec["prefill_v8_us"] <= rec["prefill_us_p10_p90"][1]
+    d8 = (arms["prefill_v8"]().float() - arms["prefill"]().float())
+    rec["prefill_v8_vs_prefill_output"] = dict(max_abs=float(d8.abs().max()), mse=float((d8 * d8).mean()))
     for a in arms:
         if not a.startswith("prefill"):
             rec[f"{a}_over_prefill"] = rec[a + "_us"] / rec["prefill_us"]
