@@ -18,6 +18,7 @@ A case is a plain dict:
 import numpy as np
 
 import kvcache_reference as kr
+import v8_reference as v8
 
 SQ_CHOICES = [1, 2, 3, 4, 5, 7, 8, 11, 13, 16]
 G_CHOICES = [1, 2, 3, 4, 5, 6, 7, 8, 9, 16]
@@ -266,6 +267,13 @@ def new_ref(orc, c):
     return kr.CacheRef(orc, c["B"], c["Hkv"], c["Dp"], cap, c["dtype"], qmax=k_qmax(c), smooth_k=c["smooth_k"])
 
 
+def new_ref_v8(orc, c):
+    """the numpy cache of the case's fp8 twin (`v_bits = 8`): the same K state, V as e4m3 codes and scales, `vhat()` what a
+    reader sees"""
+    cap = -(-c["capacity"] // kr.BLKK) * kr.BLKK
+    return v8.CacheRefV8(orc, c["B"], c["Hkv"], c["Dp"], cap, c["dtype"], qmax=k_qmax(c), smooth_k=c["smooth_k"])
+
+
 def ref_append(orc, c, ref, step, k, v):
     """append number `step` of the case into `ref`.  A uniform first append takes the dense operators' mean (`oracle.mean_seq`),
     as the cache does."""
@@ -275,8 +283,8 @@ def ref_append(orc, c, ref, step, k, v):
     ref.append(_pad(k, c), _pad(v, c), a["new_lens"])
 
 
-def replay(orc, c, kv):
-    ref = new_ref(orc, c)
+def replay(orc, c, kv, new=new_ref):
+    ref = new(orc, c)
     for step, (k, v) in enumerate(kv):
         ref_append(orc, c, ref, step, k, v)
     assert list(ref.seqlens) == list(c["lens"])
@@ -301,11 +309,12 @@ def quantised_q(orc, c, q):
     return kr.quant_q(orc, _pad(q, c), sm_scale_of(c), 127 if c["q_bits"] == 8 else 7)
 
 
-def decode_reference(orc, c, ref, q):
-    """the oracle's kernel on `ref`'s state: -> O [B, Hq, Sq, D], natural-log LSE [B, Hq, Sq], corr (dtype(q . km) or None)"""
+def decode_reference(orc, c, ref, q, v=None):
+    """the oracle's kernel on `ref`'s state: -> O [B, Hq, Sq, D], natural-log LSE [B, Hq, Sq], corr (dtype(q . km) or None).
+    `v`: the V it reads in place of `ref.v` - V^ = `ref.vhat()` for the fp8 twin"""
     q_i8, q_scale = quantised_q(orc, c, q)
-    o, lse2 = kr.oracle_decode(orc, q_i8, q_scale, ref.k_codes, ref.k_scale, ref.v, ref.seqlens, causal=c["is_causal"],
-                               out_dtype=c["dtype"])
+    o, lse2 = kr.oracle_decode(orc, q_i8, q_scale, ref.k_codes, ref.k_scale, ref.v if v is None else v, ref.seqlens,
+                               causal=c["is_causal"], out_dtype=c["dtype"])
     corr = kr.lse_correction(orc, _pad(q, c), ref.km, c["dtype"])
     return o[..., :c["D"]], kr.natural_lse(lse2, corr, sm_scale_of(c)), corr
 

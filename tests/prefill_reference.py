@@ -10,13 +10,31 @@ tests/kvcache_reference.py, which it builds on).
   over 64-key tiles per slice, then the decode call's fixed-order combine (`split_kv_decode` generalised).
 * `CASES`: the value cases of tests/test_gpu_prefill.py; tests/test_prefill_reference_cpu.py shows on every one of them that the
   numpy model stays inside the bounds (`o_bound`, `lse_bound` of kvcache_reference, unchanged, on every element).
+* `oracle_state`: the state `oracle_prefill` reads - of a `CacheRef` its own, of a `v8_reference.CacheRefV8` the K state with
+  V^ = `vhat()` as V, which is what a reader of the fp8 V cache sees.
+* the census helpers of the prefill fuzz (tests/prefill_fuzz_cases.py): what a drawn case exercises, in the kernel's own terms
+  (Q blocks, visible tiles, tiles per slice, tiles per page).
 """
+import types
+
 import numpy as np
 
 import kvcache_reference as kr
 
 BLKQ, BLKK = 128, 64
-B, HQ, HKV = 2, 4, 2  # the common shape of the cases
+B, HQ, HKV = 2, 4, 2  # the common shape of the cases: what a case that names no B / HQ / HKV of its own gets
+
+
+def shape_of(c):
+    """(B, Hq, Hkv) of a value case"""
+    return c.get("B", B), c.get("HQ", HQ), c.get("HKV", HKV)
+
+
+def oracle_state(ref):
+    """what `oracle_prefill` reads of a numpy cache: with an fp8 V cache (`CacheRefV8`) V is V^, the V a reader sees"""
+    if not hasattr(ref, "vhat"):
+        return ref
+    return types.SimpleNamespace(k_codes=ref.k_codes, k_scale=ref.k_scale, v=ref.vhat(), seqlens=ref.seqlens)
 
 
 def quant_q_blocks(orc, q, q_lens, sm_scale, qmax):
@@ -41,6 +59,7 @@ def oracle_prefill(orc, q_i8, q_scale, ref, q_lens, *, causal, out_dtype):
     nb, hq, sq, d = q_i8.shape
     o = np.zeros((nb, hq, sq, d), np.float32)
     lse2 = np.full((nb, hq, sq), -np.inf, np.float32)
+    ref = oracle_state(ref)
     k_i8, k_scale, v16 = ref.k_codes, ref.k_scale, ref.v
 
     def run(b, rows, qs, n):
@@ -61,6 +80,24 @@ def oracle_prefill(orc, q_i8, q_scale, ref, q_lens, *, causal, out_dtype):
             ni = n - ql + 1 + i
             if ni > 0:
                 run(b, slice(i, i + 1), q_scale[b:b + 1, :, i // BLKQ:i // BLKQ + 1], ni)
+    return o, lse2
+
+
+def oracle_prefill_rows(orc, q_i8, q_scale, ref, b, rows, *, q_len, causal, out_dtype):
+    """`oracle_prefill` on the sampled query rows `rows` of sequence b alone (a long context, where every row would take minutes):
+    the same per-row call on the row's visible keys with the scale of its block -> o [Hq, len(rows), D], lse2 [Hq, len(rows)]"""
+    ref = oracle_state(ref)
+    n = int(ref.seqlens[b])
+    o = np.zeros((q_i8.shape[1], len(rows), q_i8.shape[3]), np.float32)
+    lse2 = np.full((q_i8.shape[1], len(rows)), -np.inf, np.float32)
+    for j, i in enumerate(rows):
+        ni = (n - q_len + 1 + i) if causal else n
+        if i >= q_len or ni <= 0:
+            continue
+        ob, lb = orc.attn_fwd_int8_fp16(q_i8[b:b + 1, :, i:i + 1], ref.k_codes[b:b + 1, :, :ni], ref.v[b:b + 1, :, :ni],
+                                        q_scale[b:b + 1, :, i // BLKQ:i // BLKQ + 1], ref.k_scale[b:b + 1, :, :(ni + BLKK - 1) // BLKK],
+                                        causal=False, out_dtype=out_dtype, return_lse=True, tail="neg_inf")
+        o[:, j], lse2[:, j] = ob[0, :, 0], lb[0, :, 0]
     return o, lse2
 
 
@@ -163,7 +200,7 @@ CONTAINMENT_LENS, CONTAINMENT_Q_LENS, CONTAINMENT_SQ = [1, 63, 64, 65, 130], [13
 
 
 def case_id(c):
-    extra = "".join(f"-{k}{c[k]}" for k in ("q_bits", "k_bits", "smooth_k", "sm_scale") if k in c)
+    extra = "".join(f"-{k}{c[k]}" for k in ("q_bits", "k_bits", "smooth_k", "sm_scale", "B", "HQ", "HKV") if k in c)
     return f"Sq{c['Sq']}n{'_'.join(map(str, c['lens']))}" + (f"q{'_'.join(map(str, c['q_lens']))}" if "q_lens" in c else "") + \
         f"D{c['D']}{c['dtype']}{c['layout']}{extra}"
 
@@ -183,6 +220,7 @@ def build_case(orc, c):
     if key in _built:
         return _built[key]
     Sq, D, dtype = c["Sq"], c["D"], c["dtype"]
+    B, HQ, HKV = shape_of(c)
     Dp = 64 if D <= 64 else 128
     lens = np.array(c["lens"])
     q_lens = np.array(c.get("q_lens", [Sq] * B))
@@ -217,3 +255,112 @@ def chosen_splits(Sq, max_k, batch=B, hq=HQ):
     """the documented rule: max(1, min(ceil(512 / (B Hq ceil(Sq / 128))), tiles / 4, 256))"""
     tiles = (max_k + BLKK - 1) // BLKK
     return max(1, min(-(-512 // (batch * hq * ((Sq + BLKQ - 1) // BLKQ))), tiles // 4, 256))
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# census helpers: what a case of tests/prefill_fuzz_cases.py exercises.  A fuzz case names Sq, G, Hkv, B, q_lens [B] (resolved),
+# lens [B], splits, page and its append schedule; both causal flags are always run, so the causal tile counts are what counts.
+# ------------------------------------------------------------------------------------------------------------------------
+def q_blocks(c):
+    return (c["Sq"] + BLKQ - 1) // BLKQ
+
+
+def visible_tiles(c, b, qb, causal=True):
+    """tiles the Q block `qb` of sequence b walks (0: no valid row, or no key below the limit of its last valid row)"""
+    n, ql = c["lens"][b], c["q_lens"][b]
+    last = min(qb * BLKQ + BLKQ - 1, ql - 1)
+    if last < qb * BLKQ:
+        return 0
+    see = max(n - ql + 1 + last, 0) if causal else n
+    return (see + BLKK - 1) // BLKK
+
+
+def tiles_per_slice(c, b, qb, ns, causal=True):
+    return -(-visible_tiles(c, b, qb, causal) // ns)
+
+
+def effective_splits(c, ns):
+    """a slice count of the case, 0 resolved by the documented rule on the host's bound of the lengths (the rows offered)"""
+    return ns or chosen_splits(c["Sq"], max(1, sum(a["T"] for a in c["appends"])), batch=c["B"], hq=c["G"] * c["Hkv"])
+
+
+def blocks_see_different_tiles(c):
+    """distinct non-zero causal tile counts among the Q blocks of one sequence: each block gets its own tps"""
+    return max(len({visible_tiles(c, b, qb) for qb in range(q_blocks(c))} - {0}) for b in range(c["B"]))
+
+
+def slice_count_between_first_and_last_block(c):
+    """four Q blocks and a slice count above the first block's causal tiles and below the last block's"""
+    if q_blocks(c) < 4:
+        return False
+    return any(0 < visible_tiles(c, b, 0) < ns < visible_tiles(c, b, q_blocks(c) - 1)
+               for b in range(c["B"]) for ns in map(lambda s: effective_splits(c, s), c["splits"]))
+
+
+def empty_middle_block_next_to_a_full_one(c):
+    """a Q block that is not the last of the grid, past q_lens[b] of one sequence while another sequence has rows in it"""
+    return any(c["q_lens"][b] <= qb * BLKQ < c["q_lens"][b2]
+               for qb in range(1, q_blocks(c) - 1) for b in range(c["B"]) for b2 in range(c["B"]))
+
+
+def longest_slice(c):
+    """most tiles any slice of the case walks: the trips of the look-ahead loop (two tiles a trip)"""
+    return max([tiles_per_slice(c, b, qb, effective_splits(c, ns), causal) for b in range(c["B"]) for qb in range(q_blocks(c))
+                for ns in c["splits"] for causal in (False, True)] or [0])
+
+
+def slice_starts_on_odd_tile_inside_page(c):
+    """some slice with keys begins on an odd tile that is not the first of its page"""
+    tpp = c["page"] // BLKK
+    for b in range(c["B"]):
+        for qb in range(q_blocks(c)):
+            for causal in (False, True):
+                nt = visible_tiles(c, b, qb, causal)
+                for ns in c["splits"]:
+                    tps = -(-nt // effective_splits(c, ns))
+                    if any(t0 % 2 and t0 % tpp for t0 in range(tps, nt, max(tps, 1))):
+                        return True
+    return False
+
+
+def page_192_with_ragged_tiles_and_odd_tps(c):
+    """page 192 (three tiles a page), a tile count that is no multiple of 3 and an odd tps > 1 on it"""
+    if c["page"] != 192:
+        return False
+    return any(visible_tiles(c, b, qb, causal) % 3 and tiles_per_slice(c, b, qb, effective_splits(c, ns), causal) % 2
+               and tiles_per_slice(c, b, qb, effective_splits(c, ns), causal) > 1
+               for b in range(c["B"]) for qb in range(q_blocks(c)) for ns in c["splits"] for causal in (False, True))
+
+
+def combine_second_trip(c):
+    """more than 256 slices that hold keys, with hundreds of query rows per kv head"""
+    return c["Sq"] * c["G"] > 64 and max(c["splits"]) > 256 and max(visible_tiles(c, b, 0, False) for b in range(c["B"])) > 256
+
+
+def no_keys_next_to_a_full_sequence(c):
+    return any(n == 0 and c["q_lens"][b] > 0 for b, n in enumerate(c["lens"])) and \
+        any(n >= ql > 0 for n, ql in zip(c["lens"], c["q_lens"]))
+
+
+def fewer_keys_than_queries(c):
+    """0 < n < q_len: causal rows that see no key in front of rows that do"""
+    return any(0 < n < ql for n, ql in zip(c["lens"], c["q_lens"]))
+
+
+def q_len_cuts(c):
+    """where q_lens cut: the set of 'row16' (inside a 16-row block), 'wave' (a 32-row edge that is no block edge), 'block' (a
+    128-row edge), 'trailing' (whole trailing Q blocks without a valid row), 'zero'"""
+    out = set()
+    for ql in c["q_lens"]:
+        if ql == 0:
+            out.add("zero")
+        elif ql < c["Sq"]:
+            out.add("row16" if ql % 16 else "wave" if ql % BLKQ else "block")
+            if (ql + BLKQ - 1) // BLKQ < q_blocks(c):
+                out.add("trailing")
+    return out
+
+
+def key_offset_to_tile_edge(c):
+    """(n - q_len) % 64 of the sequences that have both queries and keys: the causal limits on both sides of a tile edge"""
+    return {(n - ql) % BLKK for n, ql in zip(c["lens"], c["q_lens"]) if n and ql}

@@ -6,12 +6,15 @@
   quantiser's codes and scales bit for bit, and the numpy model of the kernel (`split_kv_decode`) at the case's three slice
   counts lies inside `o_bound` / `lse_bound` of `oracle_decode` on every element.  So the GPU test asks nothing of the kernel
   that plain fp32 arithmetic in the kernel's order does not deliver.
+* The fp8 twin (`v_bits = 8`) of every case: `CacheRefV8` after the same schedule holds `quant_v_rows`' codes and scales and the
+  same K state, and the numpy model on V^ lies inside the same bounds of the oracle on V^.
 """
 import numpy as np
 import pytest
 
 import decode_fuzz_cases as fz
 import kvcache_reference as kr
+import v8_reference as v8
 
 CASES = fz.default_cases()
 
@@ -79,6 +82,37 @@ def test_numpy_kernel_model_within_the_bounds_on_every_case(oracle, case):
     for ns in c["splits"]:
         what = f"{c['name']} splits={ns}"
         o, lse2 = kr.split_kv_decode(oracle, q_i8, q_scale, ref.k_codes, ref.k_scale, ref.v, ref.seqlens, causal=c["is_causal"],
+                                     num_splits=ns or fz.chosen_splits(c), out_dtype=c["dtype"])
+        kr.check_o(o[..., :c["D"]], o_ref, c["dtype"], what)
+        kr.check_lse(kr.natural_lse(lse2, corr, sm), lse_ref, corr, sm, c["dtype"], what)
+        assert np.all(o[dead] == 0) and not np.isnan(o).any(), what
+
+
+@pytest.mark.parametrize("case", CASES, ids=lambda c: c["name"])
+def test_numpy_kernel_model_within_the_bounds_on_the_fp8_twin(oracle, case):
+    """The same cases read through an fp8 V cache: model and oracle both on V^.  Worst element over the default range: O at 0.712
+    of `o_bound` (seed11, bf16; 0.698 on the fp16 V), LSE at 0.001 of `lse_bound`."""
+    c = case
+    q, kv = fz.make_data(oracle, c)
+    ref = fz.replay(oracle, c, kv, new=fz.new_ref_v8)
+    plain = fz.replay(oracle, c, kv)
+    for name in ("k_codes", "k_scale", "v", "seqlens"):  # everything but V's format is the fp16-V cache's
+        assert np.array_equal(getattr(ref, name), getattr(plain, name)), (c["name"], name)
+    for b, (_, v_all) in enumerate(fz.concatenated(c, kv)):
+        n = v_all.shape[1]
+        if n:
+            codes, scales = v8.quant_v_rows(oracle, v_all, c["dtype"])
+            assert np.array_equal(ref.v_codes[b, :, :n, :c["D"]], codes) and not ref.v_codes[b, :, :n, c["D"]:].any(), (c["name"], b)
+            assert np.array_equal(ref.v_scale[b, :, :n].view(np.uint32), scales.view(np.uint32)), (c["name"], b)
+    vhat = ref.vhat()
+    o_ref, lse_ref, corr = fz.decode_reference(oracle, c, ref, q, v=vhat)
+    q_i8, q_scale = fz.quantised_q(oracle, c, q)
+    sm = fz.sm_scale_of(c)
+    dead = fz.blind_rows(c)
+    assert np.array_equal(np.isinf(lse_ref), dead)
+    for ns in c["splits"]:
+        what = f"{c['name']} fp8 V splits={ns}"
+        o, lse2 = kr.split_kv_decode(oracle, q_i8, q_scale, ref.k_codes, ref.k_scale, vhat, ref.seqlens, causal=c["is_causal"],
                                      num_splits=ns or fz.chosen_splits(c), out_dtype=c["dtype"])
         kr.check_o(o[..., :c["D"]], o_ref, c["dtype"], what)
         kr.check_lse(kr.natural_lse(lse2, corr, sm), lse_ref, corr, sm, c["dtype"], what)

@@ -5,6 +5,10 @@ Per case the same schedule goes into a `LowbitKVCache`, a `LowbitPagedKVCache` (
 order) and the numpy `CacheRef`.  The GPU state is compared with `CacheRef` bit for bit, and the decode with the oracle's kernel
 on `CacheRef`'s state - so the reference never passes through the code under test.  Bounds: `kvcache_reference.o_bound` /
 `lse_bound`, on every element.
+
+Every case has an fp8 twin: the same schedule into a `v_bits = 8` contiguous and paged cache.  Their state equals `CacheRefV8` bit
+for bit, their decode equals - bit for bit - that of the fp16 cache once its `v` holds V^ (computed in numpy from the fp8 cache's
+codes and scales), and lies inside the same bounds of the oracle on V^.
 """
 import os
 
@@ -13,6 +17,7 @@ import pytest
 
 import decode_fuzz_cases as fz
 import kvcache_reference as kr
+import v8_reference as v8
 from test_gpu_kvcache_decode import TDT, _np, dev  # noqa: F401
 from test_gpu_paged_kvcache import _paged
 
@@ -71,6 +76,32 @@ def _paged_vs_dense(paged, dense, c, what):
         assert torch.equal(_bits(paged.km), _bits(dense.km)), (what, "km")
 
 
+def _paged_v8(lb, c, dev, order, **kw):
+    """the fp8 twin of the paged cache: every page holds the e4m3 NaN code and NaN scales next to the K garbage"""
+    cache = lb.LowbitPagedKVCache(c["num_pages"], c["page"], c["Hkv"], c["D"], c["B"], c["max_pages"], TDT[c["dtype"]], dev,
+                                  page_order=order, v_bits=8, **kw)
+    cache.k_codes.fill_(127), cache.k_scale.fill_(float("inf")), cache.v.fill_(0xFF), cache.v_scale.fill_(float("nan"))
+    return cache
+
+
+def _v8_state_vs_ref(dense8, paged8, dense, ref8, what):
+    """the fp8 twins: v codes and v_scale bits of every valid key are `CacheRefV8`'s, the K state is the fp16-V cache's, and the
+    paged twin agrees through `gather`"""
+    codes, scales = dense8.v.cpu().numpy(), dense8.v_scale.cpu().numpy()
+    assert np.array_equal(dense8.seqlens.cpu().numpy(), ref8.seqlens) and torch.equal(paged8.seqlens, dense8.seqlens), (what, "seqlens")
+    for name in ("k_codes", "k_scale", "k_tail", "seqlens") + (("km",) if dense.km is not None else ()):
+        assert torch.equal(_bits(getattr(dense8, name)), _bits(getattr(dense, name))), (what, name, "K state of the fp8 twin")
+    for b, n in enumerate(int(x) for x in ref8.seqlens):
+        nb = (n + 63) // 64
+        assert np.array_equal(codes[b, :, :n], ref8.v_codes[b, :, :n]), (what, b, "v codes")
+        assert np.array_equal(scales[b, :, :n].view(np.uint32), ref8.v_scale[b, :, :n].view(np.uint32)), (what, b, "v scales")
+        kc, ks, vc, vs = paged8.gather(b)
+        assert torch.equal(kc[:, :n], dense8.k_codes[b, :, :n]) and torch.equal(_bits(ks[:, :nb]), _bits(dense8.k_scale[b, :, :nb])), (what, b)
+        assert torch.equal(vc[:, :n], dense8.v[b, :, :n]) and torch.equal(_bits(vs[:, :n]), _bits(dense8.v_scale[b, :, :n])), (what, b)
+    if dense.km is not None:
+        assert torch.equal(_bits(paged8.km), _bits(dense8.km)), (what, "km")
+
+
 def _cases():
     return fz.PINNED + [fz.make_case(SEED0 + s) for s in range(N)]
 
@@ -88,6 +119,9 @@ def test_fuzz_cache_and_decode(oracle, dev, case):
                    order=order, **kw)
     copies = lb.LowbitKVCache(B, Hkv, D, c["capacity"], TDT[dtype], dev, **kw) if any(a["packed"] for a in c["appends"]) else None
     ref = fz.new_ref(oracle, c)
+    dense8 = lb.LowbitKVCache(B, Hkv, D, c["capacity"], TDT[dtype], dev, v_bits=8, **kw)
+    paged8 = _paged_v8(lb, c, dev, order, **kw)
+    ref8 = fz.new_ref_v8(oracle, c)
 
     # ---- the schedule into all of them; the state after the last append (after every append for the pinned cases) -------
     last = len(c["appends"]) - 1
@@ -99,10 +133,14 @@ def test_fuzz_cache_and_decode(oracle, dev, case):
         if copies is not None:
             copies.append(tk.contiguous(), tv.contiguous(), tensor_layout=a["layout"], new_lens=tl)
         fz.ref_append(oracle, c, ref, step, k, v)
+        dense8.append(tk, tv, tensor_layout=a["layout"], new_lens=tl)
+        paged8.append(tk, tv, tensor_layout=a["layout"], new_lens=tl)
+        fz.ref_append(oracle, c, ref8, step, k, v)
         if step == last or c["name"] in PINNED_NAMES:
             what = f"{c['name']} after append {step}"
             _state_vs_ref(dense, ref, c, what)
             _paged_vs_dense(paged, dense, c, what)
+            _v8_state_vs_ref(dense8, paged8, dense, ref8, what)
             if copies is not None:  # whole tensors: a packed view leaves the bits of its contiguous copy everywhere
                 for name in ("k_codes", "k_scale", "v", "k_tail", "seqlens") + (("km",) if c["smooth_k"] else ()):
                     assert torch.equal(_bits(getattr(dense, name)), _bits(getattr(copies, name))), (what, name, "packed view")
@@ -144,3 +182,23 @@ def test_fuzz_cache_and_decode(oracle, dev, case):
             assert torch.equal(_bits(o2), _bits(o)), f"{what}: O of the {label} differs"
             if lse2 is not None:
                 assert torch.equal(_bits(lse2), _bits(lse)), f"{what}: LSE of the {label} differs"
+
+    # ---- the fp8 twin: V^ in numpy from its codes and scales into the public `v` of the fp16 cache (whose own reads are done) ---
+    vhat = v8.dequant_v(oracle, dense8.v.cpu().numpy(), dense8.v_scale.cpu().numpy())
+    assert vhat.dtype == np.float16 and dense.v.dtype == torch.float16 and tuple(dense.v.shape) == vhat.shape
+    dense.v.copy_(torch.from_numpy(vhat).to(dev))
+    o_ref, lse_ref, corr = fz.decode_reference(oracle, c, ref8, q, v=ref8.vhat())
+    for ns in c["splits"]:
+        what = f"{c['name']} fp8 V splits={ns}"
+        opts = dict(tensor_layout=layout, is_causal=c["is_causal"], sm_scale=c["sm_scale"], num_splits=ns, q_bits=c["q_bits"],
+                    return_lse=True)
+        o, lse = lb.lowbit_fa_decode(tq, dense8, **opts)
+        for label, cache in (("fp16 cache holding V^", dense), ("paged fp8 cache", paged8)):
+            o2, lse2 = lb.lowbit_fa_decode(tq, cache, **opts)
+            assert torch.equal(_bits(o2), _bits(o)), f"{what}: O of the {label} differs"
+            assert torch.equal(_bits(lse2), _bits(lse)), f"{what}: LSE of the {label} differs"
+        on = _np(canon(o))
+        assert not np.isnan(on).any(), what + ": NaN in O"
+        kr.check_o(on, o_ref, dtype, what)
+        kr.check_lse(lse.cpu().numpy(), lse_ref, corr, sm, dtype, what)
+        assert np.all(on[dead] == 0) and np.all(np.isneginf(lse.cpu().numpy()[dead])), what + ": rows that see no key"

@@ -333,10 +333,15 @@ def test_page_offsets_are_formed_in_64_bits(dev):
     assert (num_pages - 2) * page * D * 2 >= 1 << 32
     _state_equal(paged, 0, dense, 0, n, "top of a 4 GiB pool")
     assert torch.all(paged.k_codes[0] == 127) and torch.all(paged.k_codes[num_pages - 3] == 127)  # nothing landed at a wrapped offset
+    q130 = _rand(gen, (1, G * Hkv, 130, D), dtype, dev)  # and a prefill read next to the decode read: two Q blocks
     for ns in (1, 3):
         o_ref, lse_ref = lb.lowbit_fa_decode(q, dense, is_causal=True, return_lse=True, num_splits=ns)
         o, lse = lb.lowbit_fa_decode(q, paged, is_causal=True, return_lse=True, num_splits=ns)
         assert torch.equal(o.view(torch.int16), o_ref.view(torch.int16)), ns
         assert torch.equal(lse.view(torch.int32), lse_ref.view(torch.int32)), ns
+        o_ref, lse_ref = lb.lowbit_fa_prefill(q130, dense, is_causal=True, return_lse=True, num_splits=ns)
+        o, lse = lb.lowbit_fa_prefill(q130, paged, is_causal=True, return_lse=True, num_splits=ns)
+        assert torch.equal(o.view(torch.int16), o_ref.view(torch.int16)), ("prefill", ns)
+        assert torch.equal(lse.view(torch.int32), lse_ref.view(torch.int32)), ("prefill", ns)
     del paged
     torch.cuda.empty_cache()

@@ -21,7 +21,7 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 TDT = {"fp16": torch.float16, "bf16": torch.bfloat16}
-B, HQ, HKV = pr.B, pr.HQ, pr.HKV
+B, HQ, HKV = pr.B, pr.HQ, pr.HKV  # the common shape: a case that names its own is read through `pr.shape_of`
 
 
 @pytest.fixture(scope="module")
@@ -65,6 +65,7 @@ def _fill(cache, c, case, dev, **kw):
 
 def _contiguous(c, case, dev):
     import lowbit_quant_fa2_paddle_amd as lb
+    B, HQ, HKV = pr.shape_of(case)
     cache = lb.LowbitKVCache(B, HKV, case["D"], c["cap"], TDT[case["dtype"]], dev, k_bits=case.get("k_bits", 8),
                              smooth_k=case.get("smooth_k", True))
     return _fill(cache, c, case, dev)
@@ -73,6 +74,7 @@ def _contiguous(c, case, dev):
 def _paged(c, case, dev, page, slots):
     """a pool full of garbage whose pages come in a scrambled order; sequence b lives in slot slots[b]"""
     import lowbit_quant_fa2_paddle_amd as lb
+    B, HQ, HKV = pr.shape_of(case)
     max_pages = -(-c["cap"] // page)
     num_pages = 3 * max_pages + 2
     order = np.random.default_rng(page + case["Sq"]).permutation(num_pages).tolist()
@@ -109,6 +111,7 @@ def _state_is_the_reference(cache, ref, what):
 @pytest.mark.parametrize("case", pr.CASES, ids=pr.case_id)
 def test_prefill_equals_oracle(oracle, dev, case):
     import lowbit_quant_fa2_paddle_amd as lb
+    B, HQ, HKV = pr.shape_of(case)
     c = pr.build_case(oracle, case)
     Sq, D, dtype, layout = case["Sq"], case["D"], case["dtype"], case["layout"]
     cache = _contiguous(c, case, dev)
@@ -160,6 +163,7 @@ def test_paged_equals_contiguous_bit_for_bit(oracle, dev, idx, page, slots):
 def test_strided_q_equals_contiguous_q(oracle, dev, idx):
     import lowbit_quant_fa2_paddle_amd as lb
     case = pr.CASES[idx]
+    B, HQ, HKV = pr.shape_of(case)
     c = pr.build_case(oracle, case)
     cache = _contiguous(c, case, dev)
     tq = _t(c["q"], case["dtype"], dev)
@@ -227,6 +231,7 @@ def test_prefill_vs_reference_golden(oracle, dev, name):
 @pytest.mark.parametrize("case", pr.SHORT_CASES, ids=pr.case_id)
 def test_short_queries_prefill_and_decode_meet_the_same_oracle(oracle, dev, case):
     import lowbit_quant_fa2_paddle_amd as lb
+    B, HQ, HKV = pr.shape_of(case)
     c = pr.build_case(oracle, case)
     Sq, D, dtype, layout = case["Sq"], case["D"], case["dtype"], case["layout"]
     assert Sq * (HQ // HKV) <= 64

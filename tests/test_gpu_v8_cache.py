@@ -11,7 +11,9 @@ scale per key and kv head.
 5. hostile memory: rows at or past the length and unused pages hold the e4m3 NaN code and NaN / +inf scales;
 6. containment: guard bands around `v` and `v_scale`, rows outside [s0, end) keep their bytes, the device-side defences;
 7. the front end.
-Shapes stay at B <= 5, Hkv <= 3 and at most 700 keys.
+Shapes stay at B <= 5, Hkv <= 3 and at most 700 keys.  The rest is elsewhere: the schedules, packed views, page sizes and slice
+counts of the fuzzes meet the fp8 cache in tests/test_gpu_decode_fuzz.py (an fp8 twin of every case) and
+tests/test_gpu_prefill_fuzz.py (half of the cases), long contexts and offsets past 2^31 in tests/test_gpu_prefill_long.py.
 """
 import numpy as np
 import pytest

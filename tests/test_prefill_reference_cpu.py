@@ -23,7 +23,7 @@ def test_numpy_model_is_inside_the_bounds_on_every_gpu_case(oracle, case):
             worst_o = max(worst_o, kr.check_o(o, o_ref, dtype, what))
             worst_l = max(worst_l, kr.check_lse(kr.natural_lse(lse2, c["corr"], c["sm_scale"]), lse_ref, c["corr"], c["sm_scale"],
                                                 dtype, what))
-            for b in range(pr.B):  # rows past q_lens: exactly zeros and -inf
+            for b in range(pr.shape_of(case)[0]):  # rows past q_lens: exactly zeros and -inf
                 assert np.all(o[b, :, c["q_lens"][b]:] == 0) and np.all(np.isneginf(lse2[b, :, c["q_lens"][b]:])), what
     print(f"{pr.case_id(case)}: worst O ratio {worst_o:.3f}, worst LSE ratio {worst_l:.3f}")
 
