@@ -128,8 +128,12 @@ hipError_t launch_attn_decode_combine(const DecodeParams& p, int dtype, int D, h
 }
 
 // ---- host-side launchers (called from lbfa_api.hip) ----------------------------------------------------------------------
-template <class KV, int VB, class P>
-static hipError_t launch_decode(const P& p, int dtype, int D, hipStream_t stream) {
+// One launcher for the four decodes: the KV policy and the V format are the block's (CacheBlock, lbfa_common.h).
+template <class P>
+hipError_t launch_decode(const P& p, int dtype, int D, hipStream_t stream) {
+  static_assert(CacheBlock<P>::op == CacheOp::kDecode, "not a parameter block of the decode kernels");
+  using KV = std::conditional_t<CacheBlock<P>::paged, PagedKV, ContiguousKV>;
+  constexpr int VB = CacheBlock<P>::v_bits;
   dim3 grid(p.splits, p.Hkv, p.B);
   const int mb = (p.M + 15) / 16;
 #define LBFA_DEC(DT, DD, MB)                                                                                       \
@@ -151,17 +155,9 @@ static hipError_t launch_decode(const P& p, int dtype, int D, hipStream_t stream
   if (e != hipSuccess || p.splits == 1) return e;
   return launch_attn_decode_combine(p, dtype, D, stream);  // the partials are indexed by row of the call: nothing paged in them
 }
-hipError_t launch_attn_decode(const DecodeParams& p, int dtype, int D, hipStream_t stream) {
-  return launch_decode<ContiguousKV, 16>(p, dtype, D, stream);
-}
-hipError_t launch_attn_paged_decode(const PagedDecodeParams& p, int dtype, int D, hipStream_t stream) {
-  return launch_decode<PagedKV, 16>(p, dtype, D, stream);
-}
-hipError_t launch_attn_decode_v8(const V8Params<DecodeParams, const float*>& p, int dtype, int D, hipStream_t stream) {
-  return launch_decode<ContiguousKV, 8>(p, dtype, D, stream);
-}
-hipError_t launch_attn_paged_decode_v8(const V8Params<PagedDecodeParams, const float*>& p, int dtype, int D, hipStream_t stream) {
-  return launch_decode<PagedKV, 8>(p, dtype, D, stream);
-}
+template hipError_t launch_decode(const DecodeParams&, int, int, hipStream_t);
+template hipError_t launch_decode(const PagedDecodeParams&, int, int, hipStream_t);
+template hipError_t launch_decode(const V8Params<DecodeParams, const float*>&, int, int, hipStream_t);
+template hipError_t launch_decode(const V8Params<PagedDecodeParams, const float*>&, int, int, hipStream_t);
 
 }  // namespace lbfa

@@ -27,8 +27,6 @@
 
 namespace lbfa {
 
-hipError_t launch_attn_decode_combine(const DecodeParams& p, int dtype, int D, hipStream_t stream);  // attn_decode.hip
-
 template <class KV>
 struct PrefillOf;
 template <>
@@ -60,8 +58,12 @@ __global__ __launch_bounds__(256) void attn_prefill_v8_kernel(V8Params<typename 
 }
 
 // ---- host-side launchers (called from lbfa_api.hip) ----------------------------------------------------------------------
-template <class KV, int VB, class P>
-static hipError_t launch_prefill(const P& p, int dtype, int D, hipStream_t stream) {
+// One launcher for the four cached prefills: the KV policy and the V format are the block's (CacheBlock, lbfa_common.h).
+template <class P>
+hipError_t launch_prefill(const P& p, int dtype, int D, hipStream_t stream) {
+  static_assert(CacheBlock<P>::op == CacheOp::kPrefill, "not a parameter block of the prefill kernels");
+  using KV = std::conditional_t<CacheBlock<P>::paged, PagedKV, ContiguousKV>;
+  constexpr int VB = CacheBlock<P>::v_bits;
   dim3 grid((unsigned)p.nQ * (unsigned)p.splits, p.Hq, p.B);
 #define LBFA_PRE(DT, DD)                                                                                        \
   do {                                                                                                          \
@@ -75,17 +77,9 @@ static hipError_t launch_prefill(const P& p, int dtype, int D, hipStream_t strea
   if (e != hipSuccess || p.splits == 1) return e;
   return launch_attn_decode_combine(p, dtype, D, stream);  // the partials are the decode kernel's: its second launch, unchanged
 }
-hipError_t launch_attn_prefill(const PrefillParams& p, int dtype, int D, hipStream_t stream) {
-  return launch_prefill<ContiguousKV, 16>(p, dtype, D, stream);
-}
-hipError_t launch_attn_paged_prefill(const PagedPrefillParams& p, int dtype, int D, hipStream_t stream) {
-  return launch_prefill<PagedKV, 16>(p, dtype, D, stream);
-}
-hipError_t launch_attn_prefill_v8(const V8Params<PrefillParams, const float*>& p, int dtype, int D, hipStream_t stream) {
-  return launch_prefill<ContiguousKV, 8>(p, dtype, D, stream);
-}
-hipError_t launch_attn_paged_prefill_v8(const V8Params<PagedPrefillParams, const float*>& p, int dtype, int D, hipStream_t stream) {
-  return launch_prefill<PagedKV, 8>(p, dtype, D, stream);
-}
+template hipError_t launch_prefill(const PrefillParams&, int, int, hipStream_t);
+template hipError_t launch_prefill(const PagedPrefillParams&, int, int, hipStream_t);
+template hipError_t launch_prefill(const V8Params<PrefillParams, const float*>&, int, int, hipStream_t);
+template hipError_t launch_prefill(const V8Params<PagedPrefillParams, const float*>&, int, int, hipStream_t);
 
 }  // namespace lbfa

@@ -140,8 +140,12 @@ static int kvcache_append_grid_x(int T) {
   return touched > 2 ? touched - 1 : 1;
 }
 
-template <class Dst, int VB, class P>
-static hipError_t launch_append(const P& p, int dtype, int D, hipStream_t stream) {
+// One launcher for the four appends: the destination policy and the V format are the block's (CacheBlock, lbfa_common.h).
+template <class P>
+hipError_t launch_append(const P& p, int dtype, int D, hipStream_t stream) {
+  static_assert(CacheBlock<P>::op == CacheOp::kAppend, "not a parameter block of the append kernels");
+  using Dst = std::conditional_t<CacheBlock<P>::paged, PagedDst, ContiguousDst>;
+  constexpr int VB = CacheBlock<P>::v_bits;
   dim3 grid(kvcache_append_grid_x(p.T), p.Hkv, p.B);
 #define LBFA_APP(DT, DD)                                                                                         \
   do {                                                                                                           \
@@ -153,18 +157,10 @@ static hipError_t launch_append(const P& p, int dtype, int D, hipStream_t stream
 #undef LBFA_APP
   return hipGetLastError();
 }
-hipError_t launch_kvcache_append(const AppendParams& p, int dtype, int D, hipStream_t stream) {
-  return launch_append<ContiguousDst, 16>(p, dtype, D, stream);
-}
-hipError_t launch_kvcache_paged_append(const PagedAppendParams& p, int dtype, int D, hipStream_t stream) {
-  return launch_append<PagedDst, 16>(p, dtype, D, stream);
-}
-hipError_t launch_kvcache_append_v8(const V8Params<AppendParams, float*>& p, int dtype, int D, hipStream_t stream) {
-  return launch_append<ContiguousDst, 8>(p, dtype, D, stream);
-}
-hipError_t launch_kvcache_paged_append_v8(const V8Params<PagedAppendParams, float*>& p, int dtype, int D, hipStream_t stream) {
-  return launch_append<PagedDst, 8>(p, dtype, D, stream);
-}
+template hipError_t launch_append(const AppendParams&, int, int, hipStream_t);
+template hipError_t launch_append(const PagedAppendParams&, int, int, hipStream_t);
+template hipError_t launch_append(const V8Params<AppendParams, float*>&, int, int, hipStream_t);
+template hipError_t launch_append(const V8Params<PagedAppendParams, float*>&, int, int, hipStream_t);
 
 hipError_t launch_kvcache_mean(const RaggedMeanParams& p, int dtype, int B, int D, hipStream_t stream) {
   dim3 grid(p.Hkv, B);

@@ -23,22 +23,7 @@ hipError_t launch_cast_bf16_f16(const void* src, void* dst, int B, int H, int S,
 hipError_t launch_absmax(const void* x, int dtype, float* out, int B, int H, int S, int D, const int64_t* st, hipStream_t stream);
 // defined in attn_bwd.hip
 hipError_t launch_attn_bwd(const BwdParams& p, int dtype, bool quant, bool causal, hipStream_t stream);
-// defined in kvcache.hip / attn_decode.hip: one kernel body each, instantiated for the contiguous and for the paged cache
-hipError_t launch_kvcache_append(const AppendParams& p, int dtype, int D, hipStream_t stream);
-hipError_t launch_kvcache_paged_append(const PagedAppendParams& p, int dtype, int D, hipStream_t stream);
-hipError_t launch_kvcache_mean(const RaggedMeanParams& p, int dtype, int B, int D, hipStream_t stream);
-hipError_t launch_attn_decode(const DecodeParams& p, int dtype, int D, hipStream_t stream);
-hipError_t launch_attn_paged_decode(const PagedDecodeParams& p, int dtype, int D, hipStream_t stream);
-// defined in attn_prefill.hip
-hipError_t launch_attn_prefill(const PrefillParams& p, int dtype, int D, hipStream_t stream);
-hipError_t launch_attn_paged_prefill(const PagedPrefillParams& p, int dtype, int D, hipStream_t stream);
-// the same six over the fp8 V cache (the *_v8_kernel instances)
-hipError_t launch_kvcache_append_v8(const V8Params<AppendParams, float*>& p, int dtype, int D, hipStream_t stream);
-hipError_t launch_kvcache_paged_append_v8(const V8Params<PagedAppendParams, float*>& p, int dtype, int D, hipStream_t stream);
-hipError_t launch_attn_decode_v8(const V8Params<DecodeParams, const float*>& p, int dtype, int D, hipStream_t stream);
-hipError_t launch_attn_paged_decode_v8(const V8Params<PagedDecodeParams, const float*>& p, int dtype, int D, hipStream_t stream);
-hipError_t launch_attn_prefill_v8(const V8Params<PrefillParams, const float*>& p, int dtype, int D, hipStream_t stream);
-hipError_t launch_attn_paged_prefill_v8(const V8Params<PagedPrefillParams, const float*>& p, int dtype, int D, hipStream_t stream);
+// the launchers of the KV-cache kernels (kvcache.hip, attn_decode.hip, attn_prefill.hip) are declared in lbfa_common.h
 }  // namespace lbfa
 
 namespace {
@@ -933,10 +918,16 @@ int lbfa_backward_varlen(const void* q, const void* k, const void* v, const void
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// int8 KV cache and split-KV decode attention (kvcache.hip, attn_decode.hip), over a contiguous cache [B, Hkv, capacity, D] or a
-// pool of pages behind a block table.  An append and a decode call are described once each: the paged entry points state the
-// pool (Pool::paged) and the two phrases of their messages that differ, everything else is the same checks in the same order.
+// int8 KV cache and split-KV decode attention (kvcache.hip, attn_decode.hip, attn_prefill.hip), over a contiguous cache
+// [B, Hkv, capacity, D] or a pool of pages behind a block table, V as fp16 or as e4m3 codes with a scale per key.
+// An append and a cache read (decode or cached prefill) are described once each, AppendCall and ReadCall: one set of checks in one
+// order, one fill of the parameter block, one launch.  An entry point is ONE statement: it names itself and its parameter block
+// and passes its arguments in the order of its signature - the pool arguments as paged(...), v_scale beside v_cache, q_lens beside
+// seqlens.  The block is the whole choice: what the call is (paged, fp8 V, prefill), which fields are filled and which kernel
+// runs all follow from its type (lbfa::CacheBlock), so the three cannot disagree.
 // ---------------------------------------------------------------------------------------------------------------
+}  // extern "C": the templates and overloads of this section need C++ linkage
+
 namespace {
 constexpr int kDecodeMaxRows = 64;     // query rows per kv head one decode workgroup serves
 constexpr int kDecodeWaves = 1024;     // workgroups (one wave each) that fill the part: 256 CUs x 4 SIMDs
@@ -945,15 +936,21 @@ constexpr int kDecodeMaxSplits = 256;
 constexpr int64_t kPrefillMaxGridX = (1 << 24) - 1;  // x extent of the prefill and combine grids (256 threads each)
 constexpr int kPrefillGroups = 512;    // four-wave workgroups that fill the part: 256 CUs x 2
 
-// Where the keys live.  Contiguous: {false, capacity}.  Paged: {true, 0, the pool}; check_pool sets cap = max_pages * page_size.
+// Where the keys live.  Contiguous: the capacity.  Paged: the pool; check_pool sets cap = max_pages * page_size.
 struct Pool {
-  bool paged;
   int cap;  // the most keys a sequence can hold
   lbfa::PoolParams at;
 };
-int check_pool(const char* who, int B, Pool& k) {
+Pool contiguous(int capacity) { return Pool{capacity, {}}; }
+Pool paged(const int32_t* block_table, const int32_t* slots, int num_slots, int num_pages, int page_size, int max_pages_per_seq) {
+  lbfa::PoolParams at{};
+  at.block_table = block_table; at.slots = slots;
+  at.num_slots = num_slots; at.num_pages = num_pages; at.page_size = page_size; at.max_pages = max_pages_per_seq;
+  return Pool{0, at};
+}
+int check_pool(const char* who, int B, bool paged, Pool& k) {
   const lbfa::PoolParams& a = k.at;
-  if (!k.paged)
+  if (!paged)
     return k.cap > 0 && k.cap % LBFA_BLKK == 0 ? 0 : fail(LBFA_EINVAL, "%s: capacity must be a positive multiple of 64, got %d", who, k.cap);
   if (a.page_size <= 0 || a.page_size % LBFA_BLKK != 0)
     return fail(LBFA_EINVAL, "%s: page_size must be a positive multiple of 64, got %d", who, a.page_size);
@@ -968,6 +965,18 @@ int check_pool(const char* who, int B, Pool& k) {
 }
 bool pool_aligned(const Pool& k) { return aligned(k.at.block_table, 4) && aligned(k.at.slots, 4); }
 
+// V of the cache: fp16 rows {v_cache}, or - the _v8 entry points - e4m3 codes and one fp32 scale per key {v_cache, v_scale}
+struct CachedV {
+  const void* p;
+  const float* scale = nullptr;
+};
+// the sequence lengths of a read: {seqlens}, a cached prefill adds its ragged query lengths {seqlens, q_lens}
+struct Lens {
+  const int32_t* seqlens;
+  const int32_t* q_lens = nullptr;
+};
+
+// what the append entry points state, in the order of their signatures
 struct AppendCall {
   const char* who;
   Operand k_new, v_new;
@@ -976,48 +985,38 @@ struct AppendCall {
   const void* km;
   int8_t* k_codes;
   float* k_scale;
-  void *v_cache, *k_tail;
+  CachedV v;
+  void* k_tail;
   const int32_t* seqlens;
-  int B, Hkv, T, D, k_qmax;
+  int B, Hkv, T, D;
   Pool pool;
-  // fp8 V cache (the _v8 entry points): v_cache holds e4m3 codes, v_scale one fp32 per key
-  bool v8;
-  float* v_scale;
+  int k_qmax;
+  bool paged, v8;  // what the parameter block is
 };
-// what the append entry points state, in the order of their signatures; `pool` says where the keys live
-AppendCall append_call(const char* who, const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
-                       int8_t* k_codes, float* k_scale, void* v_cache, void* k_tail, const int32_t* seqlens, int B, int Hkv, int T,
-                       int D, const int64_t strides_k[3], const int64_t strides_v[3], int k_qmax, const Pool& pool) {
-  AppendCall c{};
-  c.who = who; c.k_new = dense(k_new, strides_k); c.v_new = dense(v_new, strides_v); c.dtype = dtype;
-  c.new_lens = new_lens; c.km = km; c.k_codes = k_codes; c.k_scale = k_scale; c.v_cache = v_cache; c.k_tail = k_tail;
-  c.seqlens = seqlens; c.B = B; c.Hkv = Hkv; c.T = T; c.D = D; c.k_qmax = k_qmax; c.pool = pool;
-  return c;
-}
 int check_append(AppendCall& c) {
   const char* who = c.who;
-  if (!c.k_new.p || !c.v_new.p || !c.k_codes || !c.k_scale || !c.v_cache || !c.k_tail || !c.seqlens || (c.pool.paged && !c.pool.at.block_table) ||
-      (c.v8 && !c.v_scale))
+  if (!c.k_new.p || !c.v_new.p || !c.k_codes || !c.k_scale || !c.v.p || !c.k_tail || !c.seqlens || (c.paged && !c.pool.at.block_table) ||
+      (c.v8 && !c.v.scale))
     return fail(LBFA_EINVAL, "%s: null pointer", who);
   if (c.B <= 0 || c.Hkv <= 0 || c.T <= 0) return fail(LBFA_EINVAL, "%s: empty tensor", who);
   if (int st = check_head_dim(c.D, false)) return st;
-  if (int st = check_pool(who, c.B, c.pool)) return st;
+  if (int st = check_pool(who, c.B, c.paged, c.pool)) return st;
   if (int st = check_dtype(c.dtype)) return st;
   if (int st = check_qmax(who, "k_qmax", c.k_qmax)) return st;
   if (int st = check_input16(who, "k_new", c.k_new)) return st;
   if (int st = check_input16(who, "v_new", c.v_new)) return st;
-  if (!aligned(c.k_codes, 16) || !aligned(c.v_cache, 16) || !aligned(c.k_tail, 16) || !aligned(c.km, 16) || !aligned(c.k_scale, 4) ||
+  if (!aligned(c.k_codes, 16) || !aligned(c.v.p, 16) || !aligned(c.k_tail, 16) || !aligned(c.km, 16) || !aligned(c.k_scale, 4) ||
       !aligned(c.seqlens, 4) || !aligned(c.new_lens, 4) || !pool_aligned(c.pool))
     return fail(LBFA_EINVAL, "%s: cache tensors and km must be 16-byte aligned, k_scale / seqlens / new_lens%s 4-byte aligned", who,
-                c.pool.paged ? " / block_table / slots" : "");
-  if (c.v8 && !aligned(c.v_scale, 16)) return fail(LBFA_EINVAL, "%s: v_scale must be 16-byte aligned", who);
+                c.paged ? " / block_table / slots" : "");
+  if (c.v8 && !aligned(c.v.scale, 16)) return fail(LBFA_EINVAL, "%s: v_scale must be 16-byte aligned", who);
   if (c.B > 65535 || c.Hkv > 65535) return fail(LBFA_EINVAL, "%s: grid too large", who);
   return 0;
 }
-void fill_append(lbfa::AppendParams& p, const AppendCall& c) {
+void fill(lbfa::AppendParams& p, const AppendCall& c) {
   p.k_new = (const unsigned short*)c.k_new.p; p.v_new = (const unsigned short*)c.v_new.p;
   p.new_lens = c.new_lens; p.km = (const unsigned short*)c.km;
-  p.k_codes = c.k_codes; p.k_scale = c.k_scale; p.v = (unsigned short*)c.v_cache; p.k_tail = (unsigned short*)c.k_tail;
+  p.k_codes = c.k_codes; p.k_scale = c.k_scale; p.v = (unsigned short*)const_cast<void*>(c.v.p); p.k_tail = (unsigned short*)c.k_tail;
   p.seqlens = c.seqlens;
   p.kb = c.k_new.st[0]; p.kh = c.k_new.st[1]; p.ks = c.k_new.st[2];
   p.vb = c.v_new.st[0]; p.vh = c.v_new.st[1]; p.vs = c.v_new.st[2];
@@ -1025,45 +1024,31 @@ void fill_append(lbfa::AppendParams& p, const AppendCall& c) {
   p.qmax = (float)c.k_qmax;
 }
 
-struct DecodeCall {
+// what the decode and the cached-prefill entry points state, in the order of their signatures
+struct ReadCall {
   const char* who;
   Operand q, o;
   int dtype;
   const int8_t* k_codes;
   const float* k_scale;
-  const void *v_cache, *km;
-  const int32_t* seqlens;
+  CachedV v;
+  const void* km;
+  const int32_t *seqlens, *q_lens;
   float* lse;
   void* workspace;
   size_t workspace_bytes;
-  int B, Hq, Hkv, Sq, D, max_seqlen_k, num_splits;
+  int B, Hq, Hkv, Sq, D;
+  Pool pool;
+  int max_seqlen_k, num_splits;
   double sm_scale;
   int q_qmax, is_causal;
-  Pool pool;
-  int splits;  // set by check_decode: num_splits, or the split rule's choice
-  // cached prefill (lbfa_prefill[_paged]): the same call for any Sq, with ragged query lengths
-  bool prefill;
-  const int32_t* q_lens;
-  // fp8 V cache (the _v8 entry points): v_cache holds e4m3 codes, v_scale one fp32 per key
-  bool v8;
-  const float* v_scale;
+  bool paged, v8, prefill;  // what the parameter block is
+  int splits;               // set by check_decode: num_splits, or the split rule's choice
 };
-DecodeCall decode_call(const char* who, const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const void* v_cache,
-                       const void* km, const int32_t* seqlens, void* o, float* lse, void* workspace, size_t workspace_bytes, int B,
-                       int Hq, int Hkv, int Sq, int D, int max_seqlen_k, int num_splits, const int64_t strides_q[3],
-                       const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, const Pool& pool) {
-  DecodeCall c{};
-  c.who = who; c.q = dense(q, strides_q); c.o = dense(o, strides_o); c.dtype = dtype;
-  c.k_codes = k_codes; c.k_scale = k_scale; c.v_cache = v_cache; c.km = km; c.seqlens = seqlens; c.lse = lse;
-  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
-  c.B = B; c.Hq = Hq; c.Hkv = Hkv; c.Sq = Sq; c.D = D; c.max_seqlen_k = max_seqlen_k; c.num_splits = num_splits;
-  c.sm_scale = sm_scale; c.q_qmax = q_qmax; c.is_causal = is_causal; c.pool = pool;
-  return c;
-}
-int check_decode(DecodeCall& c) {
+int check_decode(ReadCall& c) {
   const char* who = c.who;
-  if (!c.q.p || !c.o.p || !c.k_codes || !c.k_scale || !c.v_cache || !c.seqlens || (c.pool.paged && !c.pool.at.block_table) ||
-      (c.v8 && !c.v_scale))
+  if (!c.q.p || !c.o.p || !c.k_codes || !c.k_scale || !c.v.p || !c.seqlens || (c.paged && !c.pool.at.block_table) ||
+      (c.v8 && !c.v.scale))
     return fail(LBFA_EINVAL, "%s: null pointer", who);
   if (c.B <= 0 || c.Hq <= 0 || c.Hkv <= 0 || c.Sq <= 0) return fail(LBFA_EINVAL, "%s: empty tensor", who);
   if (int st = check_head_dim(c.D, false)) return st;
@@ -1072,11 +1057,11 @@ int check_decode(DecodeCall& c) {
   if (!c.prefill && M > kDecodeMaxRows)
     return fail(LBFA_EINVAL, "%s: Sq * (Hq / Hkv) = %lld query rows per kv head, the limit is %d (longer queries belong on the dense operator)",
                 who, (long long)M, kDecodeMaxRows);
-  if (int st = check_pool(who, c.B, c.pool)) return st;
+  if (int st = check_pool(who, c.B, c.paged, c.pool)) return st;
   if (c.max_seqlen_k < 1 || c.max_seqlen_k > c.pool.cap)
-    return c.pool.paged ? fail(LBFA_EINVAL, "%s: max_seqlen_k must be in [1, max_pages_per_seq * page_size], got %d (limit %d)", who,
-                               c.max_seqlen_k, c.pool.cap)
-                        : fail(LBFA_EINVAL, "%s: max_seqlen_k must be in [1, capacity], got %d (capacity %d)", who, c.max_seqlen_k, c.pool.cap);
+    return c.paged ? fail(LBFA_EINVAL, "%s: max_seqlen_k must be in [1, max_pages_per_seq * page_size], got %d (limit %d)", who,
+                          c.max_seqlen_k, c.pool.cap)
+                   : fail(LBFA_EINVAL, "%s: max_seqlen_k must be in [1, capacity], got %d (capacity %d)", who, c.max_seqlen_k, c.pool.cap);
   if (c.num_splits < 0 || c.num_splits > 65535)
     return fail(LBFA_EINVAL, "%s: num_splits must be in [0, 65535] (0: chosen by %s), got %d", who,
                 c.prefill ? "lbfa_prefill_num_splits" : "lbfa_decode_num_splits", c.num_splits);
@@ -1085,11 +1070,11 @@ int check_decode(DecodeCall& c) {
   if (!(c.sm_scale > 0.0)) return fail(LBFA_EINVAL, "%s: sm_scale must be positive", who);
   if (int st = check_input16(who, "q", c.q)) return st;
   if (!aligned(c.o, 8, 4)) return fail(LBFA_EINVAL, "%s: o must be 8-byte aligned with strides that are multiples of 4 elements", who);
-  if (!aligned(c.k_codes, 16) || !aligned(c.v_cache, 16) || !aligned(c.km, 16) || !aligned(c.k_scale, 4) || !aligned(c.seqlens, 4) ||
+  if (!aligned(c.k_codes, 16) || !aligned(c.v.p, 16) || !aligned(c.km, 16) || !aligned(c.k_scale, 4) || !aligned(c.seqlens, 4) ||
       !pool_aligned(c.pool) || !aligned(c.lse, 4) || !aligned(c.q_lens, 4))
     return fail(LBFA_EINVAL, "%s: cache tensors and km must be 16-byte aligned, k_scale / seqlens%s%s / lse 4-byte aligned", who,
-                c.prefill ? " / q_lens" : "", c.pool.paged ? " / block_table / slots" : "");
-  if (c.v8 && !aligned(c.v_scale, 16)) return fail(LBFA_EINVAL, "%s: v_scale must be 16-byte aligned", who);
+                c.prefill ? " / q_lens" : "", c.paged ? " / block_table / slots" : "");
+  if (c.v8 && !aligned(c.v.scale, 16)) return fail(LBFA_EINVAL, "%s: v_scale must be 16-byte aligned", who);
   if (c.prefill) c.splits = c.num_splits ? c.num_splits : lbfa_prefill_num_splits(c.B, c.Hq, c.Sq, c.max_seqlen_k);
   else c.splits = c.num_splits ? c.num_splits : lbfa_decode_num_splits(c.B, c.Hkv, c.max_seqlen_k);
   // prefill: grid (Q blocks x slices, Hq, B) of 256 threads, the combine's (M, Hkv, B) of 256: a launch whose gridDim.x * blockDim.x
@@ -1104,9 +1089,9 @@ int check_decode(DecodeCall& c) {
   if (c.B > 65535 || c.Hkv > 65535) return fail(LBFA_EINVAL, "%s: grid too large", who);
   return 0;
 }
-void fill_decode(lbfa::DecodeParams& p, const DecodeCall& c) {
+void fill(lbfa::DecodeParams& p, const ReadCall& c) {
   const int M = c.Sq * (c.Hq / c.Hkv);
-  p.q = (const unsigned short*)c.q.p; p.k_codes = c.k_codes; p.k_scale = c.k_scale; p.v = (const unsigned short*)c.v_cache;
+  p.q = (const unsigned short*)c.q.p; p.k_codes = c.k_codes; p.k_scale = c.k_scale; p.v = (const unsigned short*)c.v.p;
   p.km = c.lse ? (const unsigned short*)c.km : nullptr;  // km only enters the LSE correction
   p.seqlens = c.seqlens; p.o = const_cast<void*>(c.o.p); p.lse = c.lse;
   p.qb = c.q.st[0]; p.qh = c.q.st[1]; p.qs = c.q.st[2];
@@ -1122,7 +1107,67 @@ void fill_decode(lbfa::DecodeParams& p, const DecodeCall& c) {
     p.ws_ml = (float*)((char*)c.workspace + align256(rows * c.D * sizeof(float)));
   }
 }
+
+// The parameter block P of a checked call: the AppendParams / DecodeParams every block starts with, then what P adds to them - the
+// pool, the scales of the fp8 V cache, the prefill fields - by what P is.
+template <class P, class Call>
+P block_of(const Call& c) {
+  using Is = lbfa::CacheBlock<P>;
+  P p{};
+  fill(p, c);
+  if constexpr (std::is_base_of<lbfa::PoolParams, P>::value) {
+    lbfa::PoolParams& at = p;
+    at = c.pool.at;
+  }
+  if constexpr (Is::v_bits == 8) p.v_scale = const_cast<decltype(p.v_scale)>(c.v.scale);
+  if constexpr (Is::op == lbfa::CacheOp::kPrefill) {
+    p.nQ = (c.Sq + LBFA_BLKQ - 1) / LBFA_BLKQ;
+    p.q_lens = c.q_lens;
+  }
+  return p;
+}
+int check_launch(hipError_t e, const char* who) {
+  return e == hipSuccess ? LBFA_OK : fail(LBFA_ELAUNCH, "%s launch: %s", who, hipGetErrorString(e));
+}
+
+// an append into the cache that P describes
+template <class P>
+int run_append(const char* who, const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km, int8_t* k_codes,
+               float* k_scale, CachedV v, void* k_tail, const int32_t* seqlens, int B, int Hkv, int T, int D, const Pool& pool,
+               const int64_t strides_k[3], const int64_t strides_v[3], int k_qmax, void* stream) {
+  using Is = lbfa::CacheBlock<P>;
+  static_assert(Is::op == lbfa::CacheOp::kAppend, "run_append takes the parameter block of an append");
+  AppendCall c{who, dense(k_new, strides_k), dense(v_new, strides_v), dtype, new_lens, km, k_codes, k_scale, v, k_tail, seqlens,
+               B, Hkv, T, D, pool, k_qmax, Is::paged, Is::v_bits == 8};
+  if (int st = check_append(c)) return st;
+  const P p = block_of<P>(c);
+  g_err[0] = 0;
+  return check_launch(lbfa::launch_append(p, dtype, D, (hipStream_t)stream), who);
+}
+// a decode or a cached prefill over the cache that P describes
+template <class P>
+int run_read(const char* who, const void* q, int dtype, const int8_t* k_codes, const float* k_scale, CachedV v, const void* km, Lens lens,
+             void* o, float* lse, void* workspace, size_t workspace_bytes, int B, int Hq, int Hkv, int Sq, int D, const Pool& pool,
+             int max_seqlen_k, int num_splits, const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax,
+             int is_causal, void* stream) {
+  using Is = lbfa::CacheBlock<P>;
+  static_assert(Is::op != lbfa::CacheOp::kAppend, "run_read takes the parameter block of a decode or a prefill");
+  constexpr bool prefill = Is::op == lbfa::CacheOp::kPrefill;
+  ReadCall c{who, dense(q, strides_q), dense(o, strides_o), dtype, k_codes, k_scale, v, km, lens.seqlens, lens.q_lens, lse, workspace,
+             workspace_bytes, B, Hq, Hkv, Sq, D, pool, max_seqlen_k, num_splits, sm_scale, q_qmax, is_causal,
+             Is::paged, Is::v_bits == 8, prefill, 0};
+  if (int st = check_decode(c)) return st;
+  const P p = block_of<P>(c);
+  g_err[0] = 0;
+  if constexpr (prefill) return check_launch(lbfa::launch_prefill(p, dtype, D, (hipStream_t)stream), who);
+  else return check_launch(lbfa::launch_decode(p, dtype, D, (hipStream_t)stream), who);
+}
+// the parameter blocks of the fp8 V cache
+template <class Base> using AppendV8 = lbfa::V8Params<Base, float*>;
+template <class Base> using ReadV8 = lbfa::V8Params<Base, const float*>;
 }  // namespace
+
+extern "C" {
 
 int lbfa_kvcache_mean(const void* k_new, int dtype, const int32_t* new_lens, void* km, int B, int Hkv, int T, int D,
                       const int64_t strides_k[3], void* stream) {
@@ -1146,13 +1191,8 @@ int lbfa_kvcache_append(const void* k_new, const void* v_new, int dtype, const i
                         int8_t* k_codes, float* k_scale, void* v_cache, void* k_tail, const int32_t* seqlens,
                         int B, int Hkv, int T, int D, int capacity, const int64_t strides_k[3], const int64_t strides_v[3],
                         int k_qmax, void* stream) {
-  AppendCall c = append_call("lbfa_kvcache_append", k_new, v_new, dtype, new_lens, km, k_codes, k_scale, v_cache, k_tail, seqlens,
-                             B, Hkv, T, D, strides_k, strides_v, k_qmax, Pool{false, capacity, {}});
-  if (int st = check_append(c)) return st;
-  lbfa::AppendParams p{};
-  fill_append(p, c);
-  g_err[0] = 0;
-  return check_hip(lbfa::launch_kvcache_append(p, dtype, D, (hipStream_t)stream), "lbfa_kvcache_append launch");
+  return run_append<lbfa::AppendParams>("lbfa_kvcache_append", k_new, v_new, dtype, new_lens, km, k_codes, k_scale, {v_cache}, k_tail,
+                                        seqlens, B, Hkv, T, D, contiguous(capacity), strides_k, strides_v, k_qmax, stream);
 }
 
 int lbfa_kvcache_paged_append(const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
@@ -1160,17 +1200,10 @@ int lbfa_kvcache_paged_append(const void* k_new, const void* v_new, int dtype, c
                               const int32_t* block_table, const int32_t* slots, int B, int Hkv, int T, int D, int num_slots,
                               int num_pages, int page_size, int max_pages_per_seq, const int64_t strides_k[3],
                               const int64_t strides_v[3], int k_qmax, void* stream) {
-  lbfa::PoolParams at{};
-  at.block_table = block_table; at.slots = slots;
-  at.num_slots = num_slots; at.num_pages = num_pages; at.page_size = page_size; at.max_pages = max_pages_per_seq;
-  AppendCall c = append_call("lbfa_kvcache_paged_append", k_new, v_new, dtype, new_lens, km, k_codes, k_scale, v_cache, k_tail,
-                             seqlens, B, Hkv, T, D, strides_k, strides_v, k_qmax, Pool{true, 0, at});
-  if (int st = check_append(c)) return st;
-  lbfa::PagedAppendParams p{};
-  fill_append(p, c);
-  static_cast<lbfa::PoolParams&>(p) = c.pool.at;
-  g_err[0] = 0;
-  return check_hip(lbfa::launch_kvcache_paged_append(p, dtype, D, (hipStream_t)stream), "lbfa_kvcache_paged_append launch");
+  return run_append<lbfa::PagedAppendParams>("lbfa_kvcache_paged_append", k_new, v_new, dtype, new_lens, km, k_codes, k_scale, {v_cache},
+                                             k_tail, seqlens, B, Hkv, T, D,
+                                             paged(block_table, slots, num_slots, num_pages, page_size, max_pages_per_seq), strides_k,
+                                             strides_v, k_qmax, stream);
 }
 
 // the fp8 V cache: the two appends above with v_cache as e4m3 codes and v_scale, one fp32 per key, behind it
@@ -1178,15 +1211,9 @@ int lbfa_kvcache_append_v8(const void* k_new, const void* v_new, int dtype, cons
                            int8_t* k_codes, float* k_scale, uint8_t* v_cache, float* v_scale, void* k_tail, const int32_t* seqlens,
                            int B, int Hkv, int T, int D, int capacity, const int64_t strides_k[3], const int64_t strides_v[3],
                            int k_qmax, void* stream) {
-  AppendCall c = append_call("lbfa_kvcache_append_v8", k_new, v_new, dtype, new_lens, km, k_codes, k_scale, v_cache, k_tail, seqlens,
-                             B, Hkv, T, D, strides_k, strides_v, k_qmax, Pool{false, capacity, {}});
-  c.v8 = true; c.v_scale = v_scale;
-  if (int st = check_append(c)) return st;
-  lbfa::V8Params<lbfa::AppendParams, float*> p{};
-  fill_append(p, c);
-  p.v_scale = v_scale;
-  g_err[0] = 0;
-  return check_hip(lbfa::launch_kvcache_append_v8(p, dtype, D, (hipStream_t)stream), "lbfa_kvcache_append_v8 launch");
+  return run_append<AppendV8<lbfa::AppendParams>>("lbfa_kvcache_append_v8", k_new, v_new, dtype, new_lens, km, k_codes, k_scale,
+                                                  {v_cache, v_scale}, k_tail, seqlens, B, Hkv, T, D, contiguous(capacity), strides_k,
+                                                  strides_v, k_qmax, stream);
 }
 
 int lbfa_kvcache_paged_append_v8(const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
@@ -1194,19 +1221,10 @@ int lbfa_kvcache_paged_append_v8(const void* k_new, const void* v_new, int dtype
                                  const int32_t* seqlens, const int32_t* block_table, const int32_t* slots, int B, int Hkv, int T,
                                  int D, int num_slots, int num_pages, int page_size, int max_pages_per_seq,
                                  const int64_t strides_k[3], const int64_t strides_v[3], int k_qmax, void* stream) {
-  lbfa::PoolParams at{};
-  at.block_table = block_table; at.slots = slots;
-  at.num_slots = num_slots; at.num_pages = num_pages; at.page_size = page_size; at.max_pages = max_pages_per_seq;
-  AppendCall c = append_call("lbfa_kvcache_paged_append_v8", k_new, v_new, dtype, new_lens, km, k_codes, k_scale, v_cache, k_tail,
-                             seqlens, B, Hkv, T, D, strides_k, strides_v, k_qmax, Pool{true, 0, at});
-  c.v8 = true; c.v_scale = v_scale;
-  if (int st = check_append(c)) return st;
-  lbfa::V8Params<lbfa::PagedAppendParams, float*> p{};
-  fill_append(p, c);
-  static_cast<lbfa::PoolParams&>(p) = c.pool.at;
-  p.v_scale = v_scale;
-  g_err[0] = 0;
-  return check_hip(lbfa::launch_kvcache_paged_append_v8(p, dtype, D, (hipStream_t)stream), "lbfa_kvcache_paged_append_v8 launch");
+  return run_append<AppendV8<lbfa::PagedAppendParams>>("lbfa_kvcache_paged_append_v8", k_new, v_new, dtype, new_lens, km, k_codes,
+                                                       k_scale, {v_cache, v_scale}, k_tail, seqlens, B, Hkv, T, D,
+                                                       paged(block_table, slots, num_slots, num_pages, page_size, max_pages_per_seq),
+                                                       strides_k, strides_v, k_qmax, stream);
 }
 
 // The split rule: as many key slices as it takes for B * Hkv * slices one-wave workgroups to reach 1024 (four per CU), but no
@@ -1236,14 +1254,9 @@ int lbfa_decode(const void* q, int dtype, const int8_t* k_codes, const float* k_
                 const int32_t* seqlens, void* o, float* lse, void* workspace, size_t workspace_bytes,
                 int B, int Hq, int Hkv, int Sq, int D, int capacity, int max_seqlen_k, int num_splits,
                 const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream) {
-  DecodeCall c = decode_call("lbfa_decode", q, dtype, k_codes, k_scale, v_cache, km, seqlens, o, lse, workspace, workspace_bytes, B,
-                             Hq, Hkv, Sq, D, max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax, is_causal,
-                             Pool{false, capacity, {}});
-  if (int st = check_decode(c)) return st;
-  lbfa::DecodeParams p{};
-  fill_decode(p, c);
-  g_err[0] = 0;
-  return check_hip(lbfa::launch_attn_decode(p, dtype, D, (hipStream_t)stream), "lbfa_decode launch");
+  return run_read<lbfa::DecodeParams>("lbfa_decode", q, dtype, k_codes, k_scale, {v_cache}, km, {seqlens}, o, lse, workspace,
+                                      workspace_bytes, B, Hq, Hkv, Sq, D, contiguous(capacity), max_seqlen_k, num_splits, strides_q,
+                                      strides_o, sm_scale, q_qmax, is_causal, stream);
 }
 
 int lbfa_decode_paged(const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const void* v_cache, const void* km,
@@ -1251,18 +1264,10 @@ int lbfa_decode_paged(const void* q, int dtype, const int8_t* k_codes, const flo
                       void* workspace, size_t workspace_bytes, int B, int Hq, int Hkv, int Sq, int D, int num_slots, int num_pages,
                       int page_size, int max_pages_per_seq, int max_seqlen_k, int num_splits, const int64_t strides_q[3],
                       const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream) {
-  lbfa::PoolParams at{};
-  at.block_table = block_table; at.slots = slots;
-  at.num_slots = num_slots; at.num_pages = num_pages; at.page_size = page_size; at.max_pages = max_pages_per_seq;
-  DecodeCall c = decode_call("lbfa_decode_paged", q, dtype, k_codes, k_scale, v_cache, km, seqlens, o, lse, workspace,
-                             workspace_bytes, B, Hq, Hkv, Sq, D, max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax,
-                             is_causal, Pool{true, 0, at});
-  if (int st = check_decode(c)) return st;
-  lbfa::PagedDecodeParams p{};
-  fill_decode(p, c);
-  static_cast<lbfa::PoolParams&>(p) = c.pool.at;
-  g_err[0] = 0;
-  return check_hip(lbfa::launch_attn_paged_decode(p, dtype, D, (hipStream_t)stream), "lbfa_decode_paged launch");
+  return run_read<lbfa::PagedDecodeParams>("lbfa_decode_paged", q, dtype, k_codes, k_scale, {v_cache}, km, {seqlens}, o, lse,
+                                           workspace, workspace_bytes, B, Hq, Hkv, Sq, D,
+                                           paged(block_table, slots, num_slots, num_pages, page_size, max_pages_per_seq),
+                                           max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax, is_causal, stream);
 }
 
 // the fp8 V cache: the two decodes above with v_cache as e4m3 codes and v_scale, one fp32 per key, behind it
@@ -1270,16 +1275,9 @@ int lbfa_decode_v8(const void* q, int dtype, const int8_t* k_codes, const float*
                    const void* km, const int32_t* seqlens, void* o, float* lse, void* workspace, size_t workspace_bytes,
                    int B, int Hq, int Hkv, int Sq, int D, int capacity, int max_seqlen_k, int num_splits,
                    const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream) {
-  DecodeCall c = decode_call("lbfa_decode_v8", q, dtype, k_codes, k_scale, v_cache, km, seqlens, o, lse, workspace, workspace_bytes, B,
-                             Hq, Hkv, Sq, D, max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax, is_causal,
-                             Pool{false, capacity, {}});
-  c.v8 = true; c.v_scale = v_scale;
-  if (int st = check_decode(c)) return st;
-  lbfa::V8Params<lbfa::DecodeParams, const float*> p{};
-  fill_decode(p, c);
-  p.v_scale = v_scale;
-  g_err[0] = 0;
-  return check_hip(lbfa::launch_attn_decode_v8(p, dtype, D, (hipStream_t)stream), "lbfa_decode_v8 launch");
+  return run_read<ReadV8<lbfa::DecodeParams>>("lbfa_decode_v8", q, dtype, k_codes, k_scale, {v_cache, v_scale}, km, {seqlens}, o,
+                                              lse, workspace, workspace_bytes, B, Hq, Hkv, Sq, D, contiguous(capacity),
+                                              max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax, is_causal, stream);
 }
 
 int lbfa_decode_paged_v8(const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const uint8_t* v_cache,
@@ -1288,20 +1286,11 @@ int lbfa_decode_paged_v8(const void* q, int dtype, const int8_t* k_codes, const 
                          int Sq, int D, int num_slots, int num_pages, int page_size, int max_pages_per_seq, int max_seqlen_k,
                          int num_splits, const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax,
                          int is_causal, void* stream) {
-  lbfa::PoolParams at{};
-  at.block_table = block_table; at.slots = slots;
-  at.num_slots = num_slots; at.num_pages = num_pages; at.page_size = page_size; at.max_pages = max_pages_per_seq;
-  DecodeCall c = decode_call("lbfa_decode_paged_v8", q, dtype, k_codes, k_scale, v_cache, km, seqlens, o, lse, workspace,
-                             workspace_bytes, B, Hq, Hkv, Sq, D, max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax,
-                             is_causal, Pool{true, 0, at});
-  c.v8 = true; c.v_scale = v_scale;
-  if (int st = check_decode(c)) return st;
-  lbfa::V8Params<lbfa::PagedDecodeParams, const float*> p{};
-  fill_decode(p, c);
-  static_cast<lbfa::PoolParams&>(p) = c.pool.at;
-  p.v_scale = v_scale;
-  g_err[0] = 0;
-  return check_hip(lbfa::launch_attn_paged_decode_v8(p, dtype, D, (hipStream_t)stream), "lbfa_decode_paged_v8 launch");
+  return run_read<ReadV8<lbfa::PagedDecodeParams>>("lbfa_decode_paged_v8", q, dtype, k_codes, k_scale, {v_cache, v_scale}, km,
+                                                   {seqlens}, o, lse, workspace, workspace_bytes, B, Hq, Hkv, Sq, D,
+                                                   paged(block_table, slots, num_slots, num_pages, page_size, max_pages_per_seq),
+                                                   max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax, is_causal,
+                                                   stream);
 }
 
 // The split rule of the cached prefill: as many key slices as it takes for B * Hq * ceil(Sq / 128) four-wave workgroups to reach
@@ -1322,27 +1311,13 @@ size_t lbfa_prefill_workspace_bytes(int B, int Hq, int Hkv, int Sq, int D, int m
   return lbfa_decode_workspace_bytes(B, Hq, Hkv, Sq, D, max_seqlen_k, splits);  // the decode kernel's partials
 }
 
-namespace {
-void fill_prefill(int& nQ, const int*& q_lens, const DecodeCall& c) {
-  nQ = (c.Sq + LBFA_BLKQ - 1) / LBFA_BLKQ;
-  q_lens = c.q_lens;
-}
-}  // namespace
-
 int lbfa_prefill(const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const void* v_cache, const void* km,
                  const int32_t* seqlens, const int32_t* q_lens, void* o, float* lse, void* workspace, size_t workspace_bytes,
                  int B, int Hq, int Hkv, int Sq, int D, int capacity, int max_seqlen_k, int num_splits,
                  const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream) {
-  DecodeCall c = decode_call("lbfa_prefill", q, dtype, k_codes, k_scale, v_cache, km, seqlens, o, lse, workspace, workspace_bytes, B,
-                             Hq, Hkv, Sq, D, max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax, is_causal,
-                             Pool{false, capacity, {}});
-  c.prefill = true; c.q_lens = q_lens;
-  if (int st = check_decode(c)) return st;
-  lbfa::PrefillParams p{};
-  fill_decode(p, c);
-  fill_prefill(p.nQ, p.q_lens, c);
-  g_err[0] = 0;
-  return check_hip(lbfa::launch_attn_prefill(p, dtype, D, (hipStream_t)stream), "lbfa_prefill launch");
+  return run_read<lbfa::PrefillParams>("lbfa_prefill", q, dtype, k_codes, k_scale, {v_cache}, km, {seqlens, q_lens}, o, lse,
+                                       workspace, workspace_bytes, B, Hq, Hkv, Sq, D, contiguous(capacity), max_seqlen_k,
+                                       num_splits, strides_q, strides_o, sm_scale, q_qmax, is_causal, stream);
 }
 
 int lbfa_prefill_paged(const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const void* v_cache, const void* km,
@@ -1351,20 +1326,10 @@ int lbfa_prefill_paged(const void* q, int dtype, const int8_t* k_codes, const fl
                        int num_pages, int page_size, int max_pages_per_seq, int max_seqlen_k, int num_splits,
                        const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal,
                        void* stream) {
-  lbfa::PoolParams at{};
-  at.block_table = block_table; at.slots = slots;
-  at.num_slots = num_slots; at.num_pages = num_pages; at.page_size = page_size; at.max_pages = max_pages_per_seq;
-  DecodeCall c = decode_call("lbfa_prefill_paged", q, dtype, k_codes, k_scale, v_cache, km, seqlens, o, lse, workspace,
-                             workspace_bytes, B, Hq, Hkv, Sq, D, max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax,
-                             is_causal, Pool{true, 0, at});
-  c.prefill = true; c.q_lens = q_lens;
-  if (int st = check_decode(c)) return st;
-  lbfa::PagedPrefillParams p{};
-  fill_decode(p, c);
-  static_cast<lbfa::PoolParams&>(p) = c.pool.at;
-  fill_prefill(p.nQ, p.q_lens, c);
-  g_err[0] = 0;
-  return check_hip(lbfa::launch_attn_paged_prefill(p, dtype, D, (hipStream_t)stream), "lbfa_prefill_paged launch");
+  return run_read<lbfa::PagedPrefillParams>("lbfa_prefill_paged", q, dtype, k_codes, k_scale, {v_cache}, km, {seqlens, q_lens}, o,
+                                            lse, workspace, workspace_bytes, B, Hq, Hkv, Sq, D,
+                                            paged(block_table, slots, num_slots, num_pages, page_size, max_pages_per_seq),
+                                            max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax, is_causal, stream);
 }
 
 // the fp8 V cache: the two cached prefills above with v_cache as e4m3 codes and v_scale, one fp32 per key, behind it
@@ -1372,18 +1337,10 @@ int lbfa_prefill_v8(const void* q, int dtype, const int8_t* k_codes, const float
                     const void* km, const int32_t* seqlens, const int32_t* q_lens, void* o, float* lse, void* workspace,
                     size_t workspace_bytes, int B, int Hq, int Hkv, int Sq, int D, int capacity, int max_seqlen_k, int num_splits,
                     const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream) {
-  DecodeCall c = decode_call("lbfa_prefill_v8", q, dtype, k_codes, k_scale, v_cache, km, seqlens, o, lse, workspace, workspace_bytes,
-                             B, Hq, Hkv, Sq, D, max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax, is_causal,
-                             Pool{false, capacity, {}});
-  c.prefill = true; c.q_lens = q_lens;
-  c.v8 = true; c.v_scale = v_scale;
-  if (int st = check_decode(c)) return st;
-  lbfa::V8Params<lbfa::PrefillParams, const float*> p{};
-  fill_decode(p, c);
-  fill_prefill(p.nQ, p.q_lens, c);
-  p.v_scale = v_scale;
-  g_err[0] = 0;
-  return check_hip(lbfa::launch_attn_prefill_v8(p, dtype, D, (hipStream_t)stream), "lbfa_prefill_v8 launch");
+  return run_read<ReadV8<lbfa::PrefillParams>>("lbfa_prefill_v8", q, dtype, k_codes, k_scale, {v_cache, v_scale}, km,
+                                               {seqlens, q_lens}, o, lse, workspace, workspace_bytes, B, Hq, Hkv, Sq, D,
+                                               contiguous(capacity), max_seqlen_k, num_splits, strides_q, strides_o, sm_scale,
+                                               q_qmax, is_causal, stream);
 }
 
 int lbfa_prefill_paged_v8(const void* q, int dtype, const int8_t* k_codes, const float* k_scale, const uint8_t* v_cache,
@@ -1392,22 +1349,11 @@ int lbfa_prefill_paged_v8(const void* q, int dtype, const int8_t* k_codes, const
                           size_t workspace_bytes, int B, int Hq, int Hkv, int Sq, int D, int num_slots, int num_pages, int page_size,
                           int max_pages_per_seq, int max_seqlen_k, int num_splits, const int64_t strides_q[3],
                           const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream) {
-  lbfa::PoolParams at{};
-  at.block_table = block_table; at.slots = slots;
-  at.num_slots = num_slots; at.num_pages = num_pages; at.page_size = page_size; at.max_pages = max_pages_per_seq;
-  DecodeCall c = decode_call("lbfa_prefill_paged_v8", q, dtype, k_codes, k_scale, v_cache, km, seqlens, o, lse, workspace,
-                             workspace_bytes, B, Hq, Hkv, Sq, D, max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax,
-                             is_causal, Pool{true, 0, at});
-  c.prefill = true; c.q_lens = q_lens;
-  c.v8 = true; c.v_scale = v_scale;
-  if (int st = check_decode(c)) return st;
-  lbfa::V8Params<lbfa::PagedPrefillParams, const float*> p{};
-  fill_decode(p, c);
-  static_cast<lbfa::PoolParams&>(p) = c.pool.at;
-  fill_prefill(p.nQ, p.q_lens, c);
-  p.v_scale = v_scale;
-  g_err[0] = 0;
-  return check_hip(lbfa::launch_attn_paged_prefill_v8(p, dtype, D, (hipStream_t)stream), "lbfa_prefill_paged_v8 launch");
+  return run_read<ReadV8<lbfa::PagedPrefillParams>>("lbfa_prefill_paged_v8", q, dtype, k_codes, k_scale, {v_cache, v_scale}, km,
+                                                    {seqlens, q_lens}, o, lse, workspace, workspace_bytes, B, Hq, Hkv, Sq, D,
+                                                    paged(block_table, slots, num_slots, num_pages, page_size, max_pages_per_seq),
+                                                    max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax, is_causal,
+                                                    stream);
 }
 
 }  // extern "C"

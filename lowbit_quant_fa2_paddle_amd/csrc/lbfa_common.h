@@ -332,4 +332,35 @@ struct V8Params : Base {
   ScalePtr v_scale;
 };
 
+// What a parameter block of the cache kernels selects, written once: the family it belongs to, whether its keys lie in pages and
+// the bits of a cached V element.  The launchers pick the kernel instance from it and the C-ABI layer what to fill in.  Only the
+// blocks listed here have one: anything else - a base of one of them included - does not compile.
+enum class CacheOp { kAppend, kDecode, kPrefill };
+template <CacheOp OP, bool PAGED>
+struct CacheBlockOf {
+  static constexpr CacheOp op = OP;
+  static constexpr bool paged = PAGED;
+  static constexpr int v_bits = 16;
+};
+template <class P> struct CacheBlock;
+template <> struct CacheBlock<AppendParams> : CacheBlockOf<CacheOp::kAppend, false> {};
+template <> struct CacheBlock<PagedAppendParams> : CacheBlockOf<CacheOp::kAppend, true> {};
+template <> struct CacheBlock<DecodeParams> : CacheBlockOf<CacheOp::kDecode, false> {};
+template <> struct CacheBlock<PagedDecodeParams> : CacheBlockOf<CacheOp::kDecode, true> {};
+template <> struct CacheBlock<PrefillParams> : CacheBlockOf<CacheOp::kPrefill, false> {};
+template <> struct CacheBlock<PagedPrefillParams> : CacheBlockOf<CacheOp::kPrefill, true> {};
+template <class Base, class ScalePtr>
+struct CacheBlock<V8Params<Base, ScalePtr>> : CacheBlock<Base> {
+  static constexpr int v_bits = 8;
+};
+
+// The launchers of the three families: one host template each, defined and explicitly instantiated for its four blocks (contiguous
+// or paged, fp16 or fp8 V) in kvcache.hip / attn_decode.hip / attn_prefill.hip.  P is deduced exactly, never converted to a base,
+// and a block without an instantiation does not link.
+template <class P> hipError_t launch_append(const P& p, int dtype, int D, hipStream_t stream);
+template <class P> hipError_t launch_decode(const P& p, int dtype, int D, hipStream_t stream);
+template <class P> hipError_t launch_prefill(const P& p, int dtype, int D, hipStream_t stream);
+hipError_t launch_attn_decode_combine(const DecodeParams& p, int dtype, int D, hipStream_t stream);  // attn_decode.hip
+hipError_t launch_kvcache_mean(const RaggedMeanParams& p, int dtype, int B, int D, hipStream_t stream);  // kvcache.hip
+
 }  // namespace lbfa

@@ -66,18 +66,6 @@ def _append_operands(cache, k, v, tensor_layout: str):
     return ops, k, v, bht, k3, v3
 
 
-def _check_v_bits(v_bits: int) -> int:
-    if v_bits not in (16, 8):
-        raise ValueError(f"v_bits must be 16 or 8, got {v_bits}")
-    return int(v_bits)
-
-
-def _dequant_v(v, v_scale):
-    """V^ of an fp8 V cache: fp16_rne(fp32(e4m3 code) * scale), what the kernels read"""
-    import torch
-    return (v.view(torch.float8_e4m3fn).float() * v_scale[..., None]).to(torch.float16)
-
-
 def _new_lens_i32(cache, ops, new_lens, n: int, per: str):
     """new_lens of an append of n rows as an int32 tensor on the cache's device (None stays None)"""
     if new_lens is not None:
@@ -101,7 +89,78 @@ def _first_append_mean(lib, ops, k, k3, new_lens, km, B: int, H: int, T: int, D:
                                          stream), lib)
 
 
-class LowbitKVCache:
+class _CacheState:
+    """What the two caches share: the checks of the formats, the state tensors behind a leading shape, and the argument list of
+    an entry point."""
+
+    v_bits = 16  # bits of a cached V element; 8 adds `v_scale`
+
+    def _check_formats(self, k_bits: int, v_bits: int, dtype):
+        import torch
+        if k_bits not in (8, 4):
+            raise ValueError(f"k_bits must be 8 or 4, got {k_bits}")
+        if v_bits not in (16, 8):
+            raise ValueError(f"v_bits must be 16 or 8, got {v_bits}")
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError("dtype must be torch.float16 or torch.bfloat16")
+        self.v_bits, self.k_qmax = int(v_bits), 127 if k_bits == 8 else 7
+
+    def _allocate(self, num_kv_heads: int, head_dim: int, dtype, device, smooth_k: bool, blocks: int, keys: int, seqs: int):
+        """The state of `seqs` sequences whose keys lie in `blocks` runs of `keys` keys per kv head: one run per sequence
+        (contiguous) or one per page"""
+        import torch
+        self.num_kv_heads, self.head_dim = int(num_kv_heads), int(head_dim)
+        self.padded_head_dim = _padded_head_dim(self.head_dim)
+        self.dtype, self.device = dtype, torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError(f"{type(self).__name__} lives on an AMD GPU (gfx950) only; there is no CPU fallback.")
+        self.smooth_k = bool(smooth_k)
+        H, D = self.num_kv_heads, self.padded_head_dim
+
+        def zeros(shape, dt):
+            return torch.zeros(shape, dtype=dt, device=self.device)
+        self.k_codes = zeros((blocks, H, keys, D), torch.int8)
+        self.k_scale = zeros((blocks, H, keys // _lib.BLKK), torch.float32)
+        self.v = zeros((blocks, H, keys, D), torch.uint8 if self.v_bits == 8 else torch.float16)
+        if self.v_bits == 8:
+            self.v_scale = zeros((blocks, H, keys), torch.float32)
+        self.k_tail = zeros((seqs, H, _lib.BLKK, D), dtype)
+        self.km = zeros((seqs, H, D), dtype) if self.smooth_k else None
+        self.seqlens = zeros((seqs,), torch.int32)
+
+    def dequantized_v(self):
+        """Debugging aid (torch ops, read-only): fp16, the shape of `v` with the last dim cut to head_dim: the V the kernels read -
+        with `v_bits=8` V^ = fp16(fp32(code) * scale), else `v` itself.  Rows no sequence holds (contiguous cache: at or past
+        seqlens[b]) are meaningless."""
+        import torch
+        v = self.v
+        if self.v_bits == 8:
+            v = (v.view(torch.float8_e4m3fn).float() * self.v_scale[..., None]).to(torch.float16)
+        return v[..., :self.head_dim]
+
+    def _call(self, lib, name: str, head, mid, dims, tail, slot_t=None):
+        """Calls entry point `name` (+ "_v8" over an fp8 V cache) with the argument list of include/lowbit_fa.h, put together from
+        its named pieces:  head (.. v_cache), [v_scale], mid (.. seqlens[, q_lens]), [block_table, slots], dims (.. D),
+        capacity | num_slots .. max_pages_per_seq, tail (.. stream)"""
+        v8 = self.v_bits == 8
+        if isinstance(self, LowbitPagedKVCache):
+            table = (self.block_table.data_ptr(), slot_t.data_ptr() if slot_t is not None else None)
+            extent = (self.max_seqs, self.num_pages, self.page_size, self.max_pages_per_seq)
+        else:
+            table, extent = (), (self.capacity,)
+        entry = getattr(lib, name + ("_v8" if v8 else ""))
+        _lib.check(entry(*head, *((self.v_scale.data_ptr(),) if v8 else ()), *mid, *table, *dims, *extent, *tail), lib)
+
+    def _append_rows(self, lib, name: str, ops, k, v, new_lens, n: int, H: int, T: int, k3, v3, stream, slot_t=None):
+        """the append entry point `name` for n rows of T new keys"""
+        self._call(lib, name,
+                   (k.data_ptr(), v.data_ptr(), ops.dtype_code(k), new_lens.data_ptr() if new_lens is not None else None,
+                    self.km.data_ptr() if self.smooth_k else None, self.k_codes.data_ptr(), self.k_scale.data_ptr(), self.v.data_ptr()),
+                   (self.k_tail.data_ptr(), self.seqlens.data_ptr()), (n, H, T, self.padded_head_dim),
+                   (_lib.strides3(k3), _lib.strides3(v3), self.k_qmax, stream), slot_t)
+
+
+class LowbitKVCache(_CacheState):
     """Pre-allocated cache of `batch` sequences of up to `capacity` keys (rounded up to a multiple of 64).
 
     State (all on `device`): k_codes int8 [B, Hkv, cap, Dp], k_scale fp32 [B, Hkv, cap / 64], v fp16 [B, Hkv, cap, Dp],
@@ -111,37 +170,14 @@ class LowbitKVCache:
     (module docstring); with the default 16 there is no v_scale.
     No host read of `seqlens` happens anywhere: the host only tracks an upper bound of the lengths (the rows offered so far)."""
 
-    v_bits = 16  # bits of a cached V element; 8 adds `v_scale`
-
     def __init__(self, batch: int, num_kv_heads: int, head_dim: int, capacity: int, dtype, device, k_bits: int = 8,
                  smooth_k: bool = True, v_bits: int = 16):
-        import torch
-        if k_bits not in (8, 4):
-            raise ValueError(f"k_bits must be 8 or 4, got {k_bits}")
-        self.v_bits = _check_v_bits(v_bits)
-        if dtype not in (torch.float16, torch.bfloat16):
-            raise ValueError("dtype must be torch.float16 or torch.bfloat16")
+        self._check_formats(k_bits, v_bits, dtype)
         if batch <= 0 or num_kv_heads <= 0 or capacity <= 0:
             raise ValueError("batch, num_kv_heads and capacity must be positive")
-        self.batch, self.num_kv_heads, self.head_dim = int(batch), int(num_kv_heads), int(head_dim)
-        self.padded_head_dim = _padded_head_dim(self.head_dim)
+        self.batch = int(batch)
         self.capacity = (int(capacity) + _lib.BLKK - 1) // _lib.BLKK * _lib.BLKK
-        self.dtype, self.device = dtype, torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("LowbitKVCache lives on an AMD GPU (gfx950) only; there is no CPU fallback.")
-        self.k_qmax = 127 if k_bits == 8 else 7
-        self.smooth_k = bool(smooth_k)
-        B, H, C, D = self.batch, self.num_kv_heads, self.capacity, self.padded_head_dim
-        self.k_codes = torch.zeros((B, H, C, D), dtype=torch.int8, device=self.device)
-        self.k_scale = torch.zeros((B, H, C // _lib.BLKK), dtype=torch.float32, device=self.device)
-        if self.v_bits == 8:
-            self.v = torch.zeros((B, H, C, D), dtype=torch.uint8, device=self.device)
-            self.v_scale = torch.zeros((B, H, C), dtype=torch.float32, device=self.device)
-        else:
-            self.v = torch.zeros((B, H, C, D), dtype=torch.float16, device=self.device)
-        self.k_tail = torch.zeros((B, H, _lib.BLKK, D), dtype=dtype, device=self.device)
-        self.km = torch.zeros((B, H, D), dtype=dtype, device=self.device) if self.smooth_k else None
-        self.seqlens = torch.zeros((B,), dtype=torch.int32, device=self.device)
+        self._allocate(num_kv_heads, head_dim, dtype, device, smooth_k, self.batch, self.capacity, self.batch)
         self.max_seqlen = 0  # host upper bound of seqlens
         self._has_km = False
 
@@ -158,19 +194,12 @@ class LowbitKVCache:
             raise ValueError(f"appending {T} tokens to at most {self.max_seqlen} would pass the capacity {self.capacity}")
         new_lens = _new_lens_i32(self, ops, new_lens, self.batch, "sequence")
         lib = _lib.load()
-        D, code = self.padded_head_dim, ops.dtype_code(k)
         with ops.device_guard(k):
             stream = ops.stream(k)
             if self.smooth_k and not self._has_km:
-                _first_append_mean(lib, ops, k, k3, new_lens, self.km, B, H, T, D, stream)
+                _first_append_mean(lib, ops, k, k3, new_lens, self.km, B, H, T, self.padded_head_dim, stream)
                 self._has_km = True
-            v8 = self.v_bits == 8  # the _v8 entry point takes v_scale behind v_cache
-            entry = lib.lbfa_kvcache_append_v8 if v8 else lib.lbfa_kvcache_append
-            _lib.check(entry(k.data_ptr(), v.data_ptr(), code, new_lens.data_ptr() if new_lens is not None else None,
-                             self.km.data_ptr() if self.smooth_k else None, self.k_codes.data_ptr(), self.k_scale.data_ptr(),
-                             self.v.data_ptr(), *((self.v_scale.data_ptr(),) if v8 else ()), self.k_tail.data_ptr(),
-                             self.seqlens.data_ptr(), B, H, T, D, self.capacity, _lib.strides3(k3), _lib.strides3(v3), self.k_qmax,
-                             stream), lib)
+            self._append_rows(lib, "lbfa_kvcache_append", ops, k, v, new_lens, B, H, T, k3, v3, stream)
             # the kernel reads seqlens and does not advance it
             if new_lens is None:
                 self.seqlens += T
@@ -186,12 +215,6 @@ class LowbitKVCache:
         if self.km is not None:
             k = k + self.km.float()[:, :, None, :]
         return k[..., :self.head_dim]
-
-    def dequantized_v(self):
-        """Debugging aid (torch ops, read-only): fp16 [B, Hkv, capacity, head_dim], the V the kernels read - with `v_bits=8`
-        V^ = fp16(fp32(code) * scale), else `v` itself.  Rows at or past seqlens[b] are meaningless."""
-        v = _dequant_v(self.v, self.v_scale) if self.v_bits == 8 else self.v
-        return v[..., :self.head_dim]
 
 
 class PageAllocator:
@@ -265,7 +288,7 @@ def _slot_list(slots, n: int, max_seqs: int):
     return slots
 
 
-class LowbitPagedKVCache:
+class LowbitPagedKVCache(_CacheState):
     """The int8 KV cache as a pool of `num_pages` pages of `page_size` keys (a multiple of 64) shared by up to `max_seqs`
     sequences, each in a slot with a block table of up to `max_pages_per_seq` pages.
 
@@ -277,41 +300,18 @@ class LowbitPagedKVCache:
     takes its mean from its first append.  As in `LowbitKVCache` no host read of device lengths happens anywhere: pages are
     allocated for the upper bound of each length."""
 
-    v_bits = 16  # bits of a cached V element; 8 adds `v_scale`
-
     def __init__(self, num_pages: int, page_size: int, num_kv_heads: int, head_dim: int, max_seqs: int, max_pages_per_seq: int,
                  dtype, device, k_bits: int = 8, smooth_k: bool = True, page_order: Optional[Iterable[int]] = None,
                  v_bits: int = 16):
         import torch
-        if k_bits not in (8, 4):
-            raise ValueError(f"k_bits must be 8 or 4, got {k_bits}")
-        self.v_bits = _check_v_bits(v_bits)
-        if dtype not in (torch.float16, torch.bfloat16):
-            raise ValueError("dtype must be torch.float16 or torch.bfloat16")
+        self._check_formats(k_bits, v_bits, dtype)
         if num_kv_heads <= 0:
             raise ValueError("num_kv_heads must be positive")
         self.allocator = PageAllocator(num_pages, page_size, max_seqs, max_pages_per_seq, page_order)
         self.num_pages, self.page_size = self.allocator.num_pages, self.allocator.page_size
         self.max_seqs, self.max_pages_per_seq = self.allocator.max_seqs, self.allocator.max_pages_per_seq
-        self.num_kv_heads, self.head_dim = int(num_kv_heads), int(head_dim)
-        self.padded_head_dim = _padded_head_dim(self.head_dim)
-        self.dtype, self.device = dtype, torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("LowbitPagedKVCache lives on an AMD GPU (gfx950) only; there is no CPU fallback.")
-        self.k_qmax = 127 if k_bits == 8 else 7
-        self.smooth_k = bool(smooth_k)
-        N, S, H, P, D = self.num_pages, self.max_seqs, self.num_kv_heads, self.page_size, self.padded_head_dim
-        self.k_codes = torch.zeros((N, H, P, D), dtype=torch.int8, device=self.device)
-        self.k_scale = torch.zeros((N, H, P // _lib.BLKK), dtype=torch.float32, device=self.device)
-        if self.v_bits == 8:
-            self.v = torch.zeros((N, H, P, D), dtype=torch.uint8, device=self.device)
-            self.v_scale = torch.zeros((N, H, P), dtype=torch.float32, device=self.device)
-        else:
-            self.v = torch.zeros((N, H, P, D), dtype=torch.float16, device=self.device)
-        self.block_table = torch.zeros((S, self.max_pages_per_seq), dtype=torch.int32, device=self.device)
-        self.k_tail = torch.zeros((S, H, _lib.BLKK, D), dtype=dtype, device=self.device)
-        self.km = torch.zeros((S, H, D), dtype=dtype, device=self.device) if self.smooth_k else None
-        self.seqlens = torch.zeros((S,), dtype=torch.int32, device=self.device)
+        self._allocate(num_kv_heads, head_dim, dtype, device, smooth_k, self.num_pages, self.page_size, self.max_seqs)
+        self.block_table = torch.zeros((self.max_seqs, self.max_pages_per_seq), dtype=torch.int32, device=self.device)
 
     @property
     def num_free_pages(self) -> int:
@@ -334,7 +334,7 @@ class LowbitPagedKVCache:
         fresh = [i for i, s in enumerate(slots) if self.allocator.bound[s] == 0]  # rows whose sequence starts here
         changed = self.allocator.reserve(slots, T)  # raises with nothing changed
         lib = _lib.load()
-        D, code = self.padded_head_dim, ops.dtype_code(k)
+        D = self.padded_head_dim
         with ops.device_guard(k):
             stream = ops.stream(k)
             if changed:  # only the new table entries travel
@@ -347,15 +347,7 @@ class LowbitPagedKVCache:
                 _first_append_mean(lib, ops, k, k3, new_lens, km_new, n, H, T, D, stream)
                 rows = torch.tensor(fresh, dtype=torch.int64, device=self.device)
                 self.km.index_copy_(0, torch.tensor([slots[i] for i in fresh], dtype=torch.int64, device=self.device), km_new[rows])
-            v8 = self.v_bits == 8  # the _v8 entry point takes v_scale behind v_cache
-            entry = lib.lbfa_kvcache_paged_append_v8 if v8 else lib.lbfa_kvcache_paged_append
-            _lib.check(entry(
-                k.data_ptr(), v.data_ptr(), code, new_lens.data_ptr() if new_lens is not None else None,
-                self.km.data_ptr() if self.smooth_k else None, self.k_codes.data_ptr(), self.k_scale.data_ptr(), self.v.data_ptr(),
-                *((self.v_scale.data_ptr(),) if v8 else ()),
-                self.k_tail.data_ptr(), self.seqlens.data_ptr(), self.block_table.data_ptr(),
-                slot_t.data_ptr() if slot_t is not None else None, n, H, T, D, self.max_seqs, self.num_pages, self.page_size,
-                self.max_pages_per_seq, _lib.strides3(k3), _lib.strides3(v3), self.k_qmax, stream), lib)
+            self._append_rows(lib, "lbfa_kvcache_paged_append", ops, k, v, new_lens, n, H, T, k3, v3, stream, slot_t)
             # the kernel reads seqlens and does not advance it
             add = torch.full((n,), T, dtype=torch.int32, device=self.device) if new_lens is None else torch.clamp(new_lens, 0, T)
             if slot_t is None:
@@ -394,16 +386,10 @@ class LowbitPagedKVCache:
             out += (self.v_scale[idx].transpose(0, 1).reshape(H, -1).contiguous(),)
         return out
 
-    def dequantized_v(self):
-        """Debugging aid (torch ops, read-only): fp16 [num_pages, Hkv, page_size, head_dim], the V the kernels read - with
-        `v_bits=8` V^ = fp16(fp32(code) * scale), else `v` itself.  Rows no sequence holds are meaningless."""
-        v = _dequant_v(self.v, self.v_scale) if self.v_bits == 8 else self.v
-        return v[..., :self.head_dim]
-
 
 def _attend(who: str, q, cache, tensor_layout, is_causal, sm_scale, return_lse, num_splits, q_bits, slots, q_lens, prefill: bool):
-    """What `lowbit_fa_decode` and `lowbit_fa_prefill` share: the checks, the padding, the workspace and the argument lists of
-    the contiguous and the paged entry point.  `prefill` picks lbfa_prefill[_paged] (any Sq, `q_lens`) over lbfa_decode[_paged]."""
+    """What `lowbit_fa_decode` and `lowbit_fa_prefill` share: the checks, the padding, the workspace and the pieces of the
+    argument list (`_CacheState._call`).  `prefill` picks lbfa_prefill[_paged] (any Sq, `q_lens`) over lbfa_decode[_paged]."""
     ops = ops_for(q)
     if ops.name != "torch":
         raise TypeError(f"{who} takes torch tensors")
@@ -459,30 +445,15 @@ def _attend(who: str, q, cache, tensor_layout, is_causal, sm_scale, return_lse, 
     ws_bytes = workspace_bytes(B, Hq, Hkv, Sq, D, max_k, int(num_splits))
     ws = ops.empty((max(ws_bytes, 16),), ops.uint8, q)
     with ops.device_guard(q):
-        # The arguments the entry points share, in the order of include/lowbit_fa.h:
-        #   lbfa_decode:        head (q .. seqlens), out (o .. D), capacity, rest (max_seqlen_k .. stream)
-        #   lbfa_decode_paged:  head, block_table, slots, out, num_slots .. max_pages_per_seq, rest
-        #   lbfa_prefill[_paged]: the same with q_lens behind seqlens
-        #   the _v8 forms: the same with v_scale behind v_cache
-        # an fp8 V cache: the _v8 entry points, v_scale behind v_cache
-        v8 = cache.v_bits == 8
-        head = (q.data_ptr(), ops.dtype_code(q), cache.k_codes.data_ptr(), cache.k_scale.data_ptr(), cache.v.data_ptr(),
-                *((cache.v_scale.data_ptr(),) if v8 else ()),
-                cache.km.data_ptr() if cache.km is not None else None, cache.seqlens.data_ptr())
+        mid = (cache.km.data_ptr() if cache.km is not None else None, cache.seqlens.data_ptr())
         if prefill:
-            head += (q_lens.data_ptr() if q_lens is not None else None,)
-        out = (o.data_ptr(), lse.data_ptr() if return_lse else None, ws.data_ptr(), ws_bytes, B, Hq, Hkv, Sq, D)
-        rest = (max_k, int(num_splits), _lib.strides3(q3), _lib.strides3(o3), float(sm_scale), 127 if q_bits == 8 else 7,
-                1 if is_causal else 0, ops.stream(q))
-        if paged:
-            slot_t = torch.tensor(slot_list, dtype=torch.int32, device=cache.device) if slots is not None else None
-            entry = getattr(lib, ("lbfa_prefill_paged" if prefill else "lbfa_decode_paged") + ("_v8" if v8 else ""))
-            status = entry(*head, cache.block_table.data_ptr(), slot_t.data_ptr() if slot_t is not None else None,
-                           *out, cache.max_seqs, cache.num_pages, cache.page_size, cache.max_pages_per_seq, *rest)
-        else:
-            entry = getattr(lib, ("lbfa_prefill" if prefill else "lbfa_decode") + ("_v8" if v8 else ""))
-            status = entry(*head, *out, cache.capacity, *rest)
-        _lib.check(status, lib)
+            mid += (q_lens.data_ptr() if q_lens is not None else None,)
+        slot_t = torch.tensor(slot_list, dtype=torch.int32, device=cache.device) if slots is not None else None
+        cache._call(lib, ("lbfa_prefill" if prefill else "lbfa_decode") + ("_paged" if paged else ""),
+                    (q.data_ptr(), ops.dtype_code(q), cache.k_codes.data_ptr(), cache.k_scale.data_ptr(), cache.v.data_ptr()), mid,
+                    (o.data_ptr(), lse.data_ptr() if return_lse else None, ws.data_ptr(), ws_bytes, B, Hq, Hkv, Sq, D),
+                    (max_k, int(num_splits), _lib.strides3(q3), _lib.strides3(o3), float(sm_scale), 127 if q_bits == 8 else 7,
+                     1 if is_causal else 0, ops.stream(q)), slot_t)
     o = o[..., :head_dim_og]
     return (o, lse) if return_lse else o
 

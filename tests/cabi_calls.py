@@ -8,6 +8,9 @@ Argument values: `A(off)` is a pointer `off` bytes past a 256-byte aligned scrat
 3 / 2 integers a stride array {batch, head, seq} / {head, token}, everything else is passed as it is.
 """
 import ctypes
+import os
+
+import pytest
 
 from lowbit_quant_fa2_paddle_amd import _lib
 
@@ -61,6 +64,40 @@ DEFAULTS = {
                                  **_ONE_CALL, causal=0, smooth_k=1, stream=None),
 }
 
+
+# ---- the KV cache: B 1, Hkv 2, D 64; an append of T 8 rows; a decode of Sq 8 x Hq 4 over 128 keys (4 pages of 64, 2 slots of up
+# to 2 pages); a cached prefill of Sq 200 (two Q blocks) over 256 keys (8 pages of 128).  Argument names are the header's.
+def _append(table, extent):
+    return dict(k_new=P, v_new=P, dtype=_F16, new_lens=None, km=P, k_codes=P, k_scale=P, v_cache=P, k_tail=P, seqlens=P, **table,
+                B=1, Hkv=2, T=8, D=64, **extent, sk=S3, sv=S3, k_qmax=127, stream=None)
+
+
+def _read(lens, table, Sq, extent, max_seqlen_k, workspace_bytes, causal):
+    sq = (4 * Sq * 64, Sq * 64, 64)  # [B, Hq 4, Sq, D 64] contiguous
+    return dict(q=P, dtype=_F16, k_codes=P, k_scale=P, v_cache=P, km=P, seqlens=P, **lens, **table, o=P, lse=None, workspace=P,
+                workspace_bytes=workspace_bytes, B=1, Hq=4, Hkv=2, Sq=Sq, D=64, **extent, max_seqlen_k=max_seqlen_k, num_splits=2,
+                sq=sq, so=sq, sm_scale=0.125, q_qmax=127, causal=causal, stream=None)
+
+
+_TABLE = dict(block_table=P, slots=None)
+POOL = dict(num_slots=2, num_pages=4, page_size=64, max_pages_per_seq=2)
+PREFILL_POOL = dict(num_slots=2, num_pages=8, page_size=128, max_pages_per_seq=2)
+PREFILL_WS = 1 << 20
+DEFAULTS.update({
+    "lbfa_kvcache_mean": dict(k_new=P, dtype=_F16, new_lens=P, km=P, B=1, Hkv=2, T=8, D=64, sk=S3, stream=None),
+    "lbfa_kvcache_append": _append({}, dict(capacity=128)),
+    "lbfa_kvcache_paged_append": _append(_TABLE, POOL),
+    "lbfa_decode": _read({}, {}, 8, dict(capacity=128), 128, WS, 0),
+    "lbfa_decode_paged": _read({}, _TABLE, 8, POOL, 128, WS, 0),
+    "lbfa_prefill": _read(dict(q_lens=P), {}, 200, dict(capacity=256), 256, PREFILL_WS, 1),
+    "lbfa_prefill_paged": _read(dict(q_lens=None), _TABLE, 200, PREFILL_POOL, 256, PREFILL_WS, 1),
+})
+# the fp8 V cache: each entry point is its sibling with v_scale behind v_cache (as _lib.SIGNATURES derives them)
+V8 = [name for name in DEFAULTS if name + "_v8" in _lib.SIGNATURES]
+for _name in V8:
+    DEFAULTS[_name + "_v8"] = {k: v for key, val in DEFAULTS[_name].items()
+                               for k, v in ((key, val),) + ((("v_scale", P),) if key == "v_cache" else ())}
+
 _buf = ctypes.create_string_buffer(1 << 16)
 _BASE = (ctypes.addressof(_buf) + 255) & ~255
 
@@ -71,6 +108,15 @@ def _arg(v):
     if isinstance(v, tuple):
         return _lib.strides3(v) if len(v) == 3 else _lib.strides2(v)
     return v
+
+
+@pytest.fixture(scope="module")
+def lib():
+    """the built library (built first in a fresh tree); the ABI test files import this fixture"""
+    if not os.path.exists(_lib.LIB_PATH):
+        import __graft_entry__ as g
+        g.build()
+    return _lib.load()
 
 
 def call(lib, name, **overrides):
@@ -91,26 +137,12 @@ def check_table(lib, table):
 
 
 # ---- GPU side: the same keyword callers on real device pointers -----------------------------------------------------------
-# argument order of the entry points that have no default problem above (they cannot be refused without a device)
-GPU_ORDER = {
-    "lbfa_decode": ("q", "dtype", "k_codes", "k_scale", "v_cache", "km", "seqlens", "o", "lse", "workspace", "workspace_bytes",
-                    "B", "Hq", "Hkv", "Sq", "D", "capacity", "max_k", "num_splits", "sq", "so", "sm_scale", "q_qmax", "causal",
-                    "stream"),
-    "lbfa_kvcache_paged_append": ("k_new", "v_new", "dtype", "new_lens", "km", "k_codes", "k_scale", "v_cache", "k_tail", "seqlens",
-                                  "block_table", "slots", "B", "Hkv", "T", "D", "num_slots", "num_pages", "page_size", "max_pages",
-                                  "sk", "sv", "k_qmax", "stream"),
-    "lbfa_decode_paged": ("q", "dtype", "k_codes", "k_scale", "v_cache", "km", "seqlens", "block_table", "slots", "o", "lse",
-                          "workspace", "workspace_bytes", "B", "Hq", "Hkv", "Sq", "D", "num_slots", "num_pages", "page_size",
-                          "max_pages", "max_k", "num_splits", "sq", "so", "sm_scale", "q_qmax", "causal", "stream"),
-}
-
-
 def call_gpu(lib, name, **kwargs):
-    """One launching call of `name` with EVERY argument given by keyword (the names of DEFAULTS / GPU_ORDER, any order): device
+    """One launching call of `name` with EVERY argument given by keyword (the names of DEFAULTS, any order): device
     pointers as integers or None, stride arrays as tuples.  Nothing is taken from the default problem - its pointers are host
     scratch - so a missing or misspelt argument is an error here, never a launch.  Raises as the front end does on a non-zero
     status."""
-    order = tuple(DEFAULTS[name]) if name in DEFAULTS else GPU_ORDER[name]
+    order = tuple(DEFAULTS[name])
     assert set(kwargs) == set(order), (name, sorted(set(order) ^ set(kwargs)))
     assert not any(isinstance(v, A) for v in kwargs.values()), name
     _lib.check(getattr(lib, name)(*[_arg(kwargs[k]) for k in order]), lib)

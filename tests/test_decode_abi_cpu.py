@@ -5,37 +5,10 @@ import os
 
 import pytest
 
-import cabi_calls
-from cabi_calls import A, P, S3
+from cabi_calls import A, call, check_table, lib  # noqa: F401 (lib: the fixture)
 
+# the default problems (cabi_calls.DEFAULTS): B 1, Hkv 2, D 64, T / Sq 8, capacity 128
 NEW = ["lbfa_kvcache_mean", "lbfa_kvcache_append", "lbfa_decode_num_splits", "lbfa_decode_workspace_bytes", "lbfa_decode"]
-WS = 1 << 15
-# name -> arguments in ABI order with the values of a small valid problem: B 1, Hkv 2, D 64, T / Sq 8, capacity 128
-DEFAULTS = {
-    "lbfa_kvcache_mean": dict(k_new=P, dtype=0, new_lens=P, km=P, B=1, Hkv=2, T=8, D=64, sk=S3, stream=None),
-    "lbfa_kvcache_append": dict(k_new=P, v_new=P, dtype=0, new_lens=None, km=P, k_codes=P, k_scale=P, v_cache=P, k_tail=P,
-                                seqlens=P, B=1, Hkv=2, T=8, D=64, capacity=128, sk=S3, sv=S3, k_qmax=127, stream=None),
-    "lbfa_decode": dict(q=P, dtype=0, k_codes=P, k_scale=P, v_cache=P, km=P, seqlens=P, o=P, lse=None, workspace=P,
-                        workspace_bytes=WS, B=1, Hq=4, Hkv=2, Sq=8, D=64, capacity=128, max_seqlen_k=128, num_splits=2,
-                        sq=(2048, 512, 64), so=(2048, 512, 64), sm_scale=0.125, q_qmax=127, causal=0, stream=None),
-}
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from lowbit_quant_fa2_paddle_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
-
-
-def call(lib, name, **overrides):
-    args = dict(DEFAULTS[name])
-    assert overrides and set(overrides) <= set(args), (name, overrides)
-    args.update(overrides)
-    st = getattr(lib, name)(*[cabi_calls._arg(v) for v in args.values()])
-    return st, lib.lbfa_last_error().decode()
 
 
 def test_new_symbols_are_exported_and_declared(lib):
@@ -121,10 +94,7 @@ SINGLE_FAULT = [
 
 def test_single_fault_table(lib):
     from lowbit_quant_fa2_paddle_amd import _lib
-    for name, overrides, message in SINGLE_FAULT:
-        st, msg = call(lib, name, **overrides)
-        assert st == _lib.LBFA_EINVAL, (name, overrides, st, msg)
-        assert msg == message, (name, overrides, msg)
+    check_table(lib, SINGLE_FAULT)
     with pytest.raises(ValueError, match="the limit is 64"):
         _lib.check(call(lib, "lbfa_decode", Sq=33)[0], lib)
 
@@ -185,3 +155,98 @@ def test_front_end_is_exported_and_forward_only():
     cache = object.__new__(lb.LowbitKVCache)  # no device needed: the grad check comes first
     with pytest.raises(RuntimeError, match="forward-only"):
         lb.lowbit_fa_decode(q, cache)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the ORDER of the checks: calls with two faults that are neighbours in check_append / check_decode - the earlier check's
+# message wins.  Over the contiguous and the paged entry point and their _v8 siblings; a fault is a dict of overrides, or
+# {paged: overrides} where the two layouts differ.  The texts are those of the library before the cache section of
+# lbfa_api.hip described an append and a read once; {name} is the entry point, {lens} / {ids} what the prefill / paged forms add.
+# ------------------------------------------------------------------------------------------------------------------------
+_BAD_POOL = {False: dict(capacity=100), True: dict(page_size=96)}
+_POOL_TEXT = {False: "{name}: capacity must be a positive multiple of 64, got 100", True: "{name}: page_size must be a positive multiple of 64, got 96"}
+_HUGE = {False: dict(B=65536, workspace_bytes=1 << 44), True: dict(B=65536, num_slots=65536, workspace_bytes=1 << 44)}
+APPEND_ORDER = [  # (the earlier fault, the later fault, the message: the earlier one's)
+    (dict(k_codes=None), dict(T=0), "{name}: null pointer"),
+    (dict(T=0), dict(D=80), "{name}: empty tensor"),
+    (dict(D=80), _BAD_POOL, "Unsupported head_dim: 80"),
+    (_BAD_POOL, dict(dtype=7), _POOL_TEXT),
+    (dict(dtype=7), dict(k_qmax=15), "Input tensors must be in dtype of float16 or bfloat16"),
+    (dict(k_qmax=15), dict(k_new=A(2)), "{name}: k_qmax must be 127 (int8) or 7 (int4 range), got 15"),
+    (dict(k_new=A(2)), dict(sv=(1024, 512, 60)), "{name}: k_new must be 16-byte aligned with strides that are multiples of 8 elements"),
+    (dict(sv=(1024, 512, 60)), dict(k_codes=A(8)), "{name}: v_new must be 16-byte aligned with strides that are multiples of 8 elements"),
+    (dict(k_codes=A(8)), dict(Hkv=65536), "{name}: cache tensors and km must be 16-byte aligned, k_scale / seqlens / new_lens{ids} 4-byte aligned"),
+]
+APPEND_ORDER_PAGED = [  # inside check_pool
+    (dict(page_size=96), dict(num_pages=0), "{name}: page_size must be a positive multiple of 64, got 96"),
+    (dict(num_pages=0), dict(page_size=1 << 30), "{name}: num_pages, num_slots and max_pages_per_seq must be at least 1, got 0, 2 and 2"),
+    (dict(page_size=1 << 30), dict(B=3), "{name}: max_pages_per_seq * page_size must stay below 2^31 keys"),
+    (dict(B=3), dict(dtype=7), "{name}: B (3) exceeds num_slots (2)"),
+]
+APPEND_ORDER_V8 = [  # the alignment of v_scale sits between the cache tensors' and the grid
+    (dict(k_codes=A(8)), dict(v_scale=A(4)), "{name}: cache tensors and km must be 16-byte aligned, k_scale / seqlens / new_lens{ids} 4-byte aligned"),
+    (dict(v_scale=A(4)), dict(Hkv=65536), "{name}: v_scale must be 16-byte aligned"),
+]
+READ_ORDER = [
+    (dict(q=None), dict(Sq=0), "{name}: null pointer"),
+    (dict(Sq=0), dict(D=96), "{name}: empty tensor"),
+    (dict(D=96), dict(Hq=3), "Unsupported head_dim: 96"),
+    (dict(Hq=3), _BAD_POOL, "num_qo_heads (3) must be divisible by num_kv_heads (2)"),
+    (_BAD_POOL, dict(max_seqlen_k=0), _POOL_TEXT),
+    (dict(max_seqlen_k=0), dict(num_splits=-1), {False: "{name}: max_seqlen_k must be in [1, capacity], got 0 (capacity {keys})",
+                                                 True: "{name}: max_seqlen_k must be in [1, max_pages_per_seq * page_size], got 0 (limit {keys})"}),
+    (dict(num_splits=-1), dict(dtype=2), "{name}: num_splits must be in [0, 65535] (0: chosen by lbfa_{op}_num_splits), got -1"),
+    (dict(dtype=2), dict(q_qmax=8), "Input tensors must be in dtype of float16 or bfloat16"),
+    (dict(q_qmax=8), dict(sm_scale=0.0), "{name}: q_qmax must be 127 (int8) or 7 (int4 range), got 8"),
+    (dict(sm_scale=0.0), dict(q=A(8)), "{name}: sm_scale must be positive"),
+    (dict(q=A(8)), dict(o=A(4)), "{name}: q must be 16-byte aligned with strides that are multiples of 8 elements"),
+    (dict(o=A(4)), dict(k_codes=A(8)), "{name}: o must be 8-byte aligned with strides that are multiples of 4 elements"),
+    (dict(k_codes=A(8)), dict(workspace_bytes=16), "{name}: cache tensors and km must be 16-byte aligned, k_scale / seqlens{lens}{ids} / lse 4-byte aligned"),
+    (dict(workspace_bytes=16), dict(workspace=A(8)), "{name}: workspace too small (16 < {need})"),
+    (dict(workspace=A(8)), _HUGE, "{name}: workspace must be 16-byte aligned"),
+    (dict(workspace=None), _HUGE, "{name}: null pointer"),
+]
+READ_ORDER_DECODE = [  # the row limit sits between the GQA check and the pool's
+    (dict(Hq=3), dict(Sq=33), "num_qo_heads (3) must be divisible by num_kv_heads (2)"),
+    (dict(Sq=33), _BAD_POOL, "{name}: Sq * (Hq / Hkv) = 66 query rows per kv head, the limit is 64 (longer queries belong on the dense operator)"),
+]
+READ_ORDER_PREFILL = [  # the grid of the prefill kernel and of the combine sits between the alignments and the workspace
+    (dict(k_codes=A(8)), dict(Sq=257 * 128, num_splits=65535), "{name}: cache tensors and km must be 16-byte aligned, k_scale / seqlens{lens}{ids} / lse 4-byte aligned"),
+    (dict(Sq=257 * 128, num_splits=65535), dict(workspace_bytes=16),
+     "{name}: grid too large (Sq * (Hq / Hkv) and ceil(Sq / 128) * num_splits must stay below 2^24, Hq below 65536)"),
+]
+READ_ORDER_V8 = [
+    (dict(k_codes=A(8)), dict(v_scale=A(4)), "{name}: cache tensors and km must be 16-byte aligned, k_scale / seqlens{lens}{ids} / lse 4-byte aligned"),
+    (dict(v_scale=A(4)), dict(workspace_bytes=16), "{name}: v_scale must be 16-byte aligned"),
+]
+
+
+def _check_order(lib, names, tables):
+    """every (earlier, later, message) of the tables that apply to a name: each fault alone is refused, the later one with
+    another message, and both together give the earlier one's"""
+    from lowbit_quant_fa2_paddle_amd import _lib
+    for name in names:
+        paged, prefill = "paged" in name, "prefill" in name
+        words = dict(name=name, ids=" / block_table / slots" if paged else "", lens=" / q_lens" if prefill else "",
+                     op="prefill" if prefill else "decode", keys=256 if prefill else 128, need=435200 if prefill else 17408)
+        rows = [r for applies, table in tables for r in table if applies(name)]
+        assert rows, name
+        for first, second, message in rows:
+            first, second, message = (x[paged] if set(x) == {False, True} else x for x in (first, second, message))
+            message = message.format(**words)
+            assert call(lib, name, **first) == (_lib.LBFA_EINVAL, message), (name, first)
+            st, alone = call(lib, name, **second)
+            assert st == _lib.LBFA_EINVAL and alone != message, (name, second, alone)
+            assert call(lib, name, **first, **second) == (_lib.LBFA_EINVAL, message), (name, first, second)
+
+
+def test_append_checks_come_in_order(lib):
+    appends = ["lbfa_kvcache_append", "lbfa_kvcache_paged_append", "lbfa_kvcache_append_v8", "lbfa_kvcache_paged_append_v8"]
+    _check_order(lib, appends, [(lambda n: True, APPEND_ORDER), (lambda n: "paged" in n, APPEND_ORDER_PAGED),
+                                (lambda n: n.endswith("_v8"), APPEND_ORDER_V8)])
+
+
+def test_read_checks_come_in_order(lib):
+    reads = [op + layout + v for op in ("lbfa_decode", "lbfa_prefill") for layout in ("", "_paged") for v in ("", "_v8")]
+    _check_order(lib, reads, [(lambda n: True, READ_ORDER), (lambda n: "decode" in n, READ_ORDER_DECODE),
+                              (lambda n: "prefill" in n, READ_ORDER_PREFILL), (lambda n: n.endswith("_v8"), READ_ORDER_V8)])

@@ -606,7 +606,7 @@ def test_strided_decode_output_by_ctypes(monkeypatch, dev, dtype, D, Sq, causal,
     call_gpu(lib, "lbfa_decode", q=q.data_ptr(), dtype=_lib.LBFA_F16 if dtype == "fp16" else _lib.LBFA_BF16,
              k_codes=cache.k_codes.data_ptr(), k_scale=cache.k_scale.data_ptr(), v_cache=cache.v.data_ptr(), km=cache.km.data_ptr(),
              seqlens=cache.seqlens.data_ptr(), o=o.data_ptr(), lse=lse.data_ptr(), workspace=ws.data_ptr() if ws is not None else None,
-             workspace_bytes=nbytes, B=Bc, Hq=Hq, Hkv=HKV, Sq=Sq, D=D, capacity=cap, max_k=max_k, num_splits=ns,
+             workspace_bytes=nbytes, B=Bc, Hq=Hq, Hkv=HKV, Sq=Sq, D=D, capacity=cap, max_seqlen_k=max_k, num_splits=ns,
              sq=tuple(q.stride()[:3]), so=so, sm_scale=D ** -0.5, q_qmax=127, causal=int(causal),
              stream=torch.cuda.current_stream(dev).cuda_stream)
     torch.cuda.synchronize()

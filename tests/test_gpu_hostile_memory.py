@@ -444,7 +444,7 @@ def _paged_args(cache, lib, dev, dtype):
     return dict(dtype=_lib.LBFA_F16 if dtype == "fp16" else _lib.LBFA_BF16, km=cache.km.data_ptr(), k_codes=cache.k_codes.data_ptr(),
                 k_scale=cache.k_scale.data_ptr(), v_cache=cache.v.data_ptr(), seqlens=cache.seqlens.data_ptr(), Hkv=HKV,
                 D=cache.padded_head_dim, num_slots=cache.max_seqs, num_pages=cache.num_pages, page_size=cache.page_size,
-                max_pages=cache.max_pages_per_seq, stream=torch.cuda.current_stream(dev).cuda_stream)
+                max_pages_per_seq=cache.max_pages_per_seq, stream=torch.cuda.current_stream(dev).cuda_stream)
 
 
 @pytest.mark.parametrize("dtype,D,page", [("fp16", 64, 64), ("bf16", 128, 128)])
@@ -533,7 +533,7 @@ def test_paged_decode_clamps_corrupt_ids(monkeypatch, dev, dtype, D, page, ns):
         ws = arena.allocate((max(nbytes, 16),), torch.uint8)
         args = _paged_args(cache, lib, dev, dtype)
         call_gpu(lib, "lbfa_decode_paged", q=q.data_ptr(), block_table=tbl.data_ptr(), slots=sl.data_ptr(), o=o.data_ptr(),
-                 lse=lse.data_ptr(), workspace=ws.data_ptr(), workspace_bytes=nbytes, B=num_slots, Hq=Hq, Sq=Sq, max_k=n, num_splits=ns,
+                 lse=lse.data_ptr(), workspace=ws.data_ptr(), workspace_bytes=nbytes, B=num_slots, Hq=Hq, Sq=Sq, max_seqlen_k=n, num_splits=ns,
                  sq=tuple(q.stride()[:3]), so=tuple(o.stride()[:3]), sm_scale=D ** -0.5, q_qmax=127, causal=1, **args)
         torch.cuda.synchronize()
         return o, lse

@@ -204,7 +204,7 @@ def test_paged_prefill_clamps_corrupt_ids(monkeypatch, dev, dtype, D, page, ns):
         a = _paged_args(cache, lib, dev, dtype)
         st = lib.lbfa_prefill_paged(q.data_ptr(), a["dtype"], a["k_codes"], a["k_scale"], a["v_cache"], a["km"], a["seqlens"], None,
                                     tbl.data_ptr(), sl.data_ptr(), o.data_ptr(), lse.data_ptr(), ws.data_ptr(), nbytes, num_slots, HQ,
-                                    HKV, SQ, D, a["num_slots"], a["num_pages"], a["page_size"], a["max_pages"], n, ns,
+                                    HKV, SQ, D, a["num_slots"], a["num_pages"], a["page_size"], a["max_pages_per_seq"], n, ns,
                                     _lib.strides3(q.stride()[:3]), _lib.strides3(o.stride()[:3]), D ** -0.5, 127, 1, a["stream"])
         _lib.check(st, lib)
         torch.cuda.synchronize()

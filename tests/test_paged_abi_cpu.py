@@ -6,43 +6,13 @@ import os
 
 import pytest
 
-import cabi_calls
-from cabi_calls import A, P, S3
+from cabi_calls import DEFAULTS, A, call, check_table, lib  # noqa: F401 (lib: the fixture)
 
+# the default problems (cabi_calls.DEFAULTS): B 1, Hkv 2, D 64, T / Sq 8, 4 pages of 64 keys, 2 slots of up to 2 pages
 NEW = ["lbfa_kvcache_paged_append", "lbfa_decode_paged"]
-WS = 1 << 15
-# name -> arguments in ABI order with the values of a small valid problem: B 1, Hkv 2, D 64, T / Sq 8, 4 pages of 64 keys,
-# 2 slots of up to 2 pages
-POOL = dict(num_slots=2, num_pages=4, page_size=64, max_pages_per_seq=2)
-DEFAULTS = {
-    "lbfa_kvcache_paged_append": dict(k_new=P, v_new=P, dtype=0, new_lens=None, km=P, k_codes=P, k_scale=P, v_cache=P, k_tail=P,
-                                      seqlens=P, block_table=P, slots=None, B=1, Hkv=2, T=8, D=64, **POOL, sk=S3, sv=S3,
-                                      k_qmax=127, stream=None),
-    "lbfa_decode_paged": dict(q=P, dtype=0, k_codes=P, k_scale=P, v_cache=P, km=P, seqlens=P, block_table=P, slots=None, o=P,
-                              lse=None, workspace=P, workspace_bytes=WS, B=1, Hq=4, Hkv=2, Sq=8, D=64, **POOL, max_seqlen_k=128,
-                              num_splits=2, sq=(2048, 512, 64), so=(2048, 512, 64), sm_scale=0.125, q_qmax=127, causal=0,
-                              stream=None),
-}
 APP, DEC = NEW
 APP_ALIGN = "lbfa_kvcache_paged_append: cache tensors and km must be 16-byte aligned, k_scale / seqlens / new_lens / block_table / slots 4-byte aligned"
 DEC_ALIGN = "lbfa_decode_paged: cache tensors and km must be 16-byte aligned, k_scale / seqlens / block_table / slots / lse 4-byte aligned"
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from lowbit_quant_fa2_paddle_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
-
-
-def call(lib, name, **overrides):
-    args = dict(DEFAULTS[name])
-    assert overrides and set(overrides) <= set(args), (name, overrides)
-    args.update(overrides)
-    st = getattr(lib, name)(*[cabi_calls._arg(v) for v in args.values()])
-    return st, lib.lbfa_last_error().decode()
 
 
 def test_new_symbols_are_exported_and_declared(lib):
@@ -139,10 +109,7 @@ SINGLE_FAULT = [
 
 def test_single_fault_table(lib):
     from lowbit_quant_fa2_paddle_amd import _lib
-    for name, overrides, message in SINGLE_FAULT:
-        st, msg = call(lib, name, **overrides)
-        assert st == _lib.LBFA_EINVAL, (name, overrides, st, msg)
-        assert msg == message, (name, overrides, msg)
+    check_table(lib, SINGLE_FAULT)
     with pytest.raises(ValueError, match="exceeds num_slots"):
         _lib.check(call(lib, DEC, B=3)[0], lib)
 

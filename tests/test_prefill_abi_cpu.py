@@ -5,39 +5,10 @@ import os
 
 import pytest
 
-import cabi_calls
-from cabi_calls import A, P
+from cabi_calls import A, call, check_table, lib  # noqa: F401 (lib: the fixture)
 
+# the default problems (cabi_calls.DEFAULTS): B 1, Hq 4, Hkv 2, Sq 200 (two Q blocks), D 64, 256 keys of room (pages of 128)
 NEW = ["lbfa_prefill_num_splits", "lbfa_prefill_workspace_bytes", "lbfa_prefill", "lbfa_prefill_paged"]
-WS = 1 << 20
-SQ = (4 * 200 * 64, 200 * 64, 64)  # [B, Hq 4, Sq 200, D 64] contiguous
-# name -> arguments in ABI order with the values of a small valid problem: B 1, Hq 4, Hkv 2, Sq 200 (two Q blocks), D 64
-DEFAULTS = {
-    "lbfa_prefill": dict(q=P, dtype=0, k_codes=P, k_scale=P, v_cache=P, km=P, seqlens=P, q_lens=P, o=P, lse=None, workspace=P,
-                         workspace_bytes=WS, B=1, Hq=4, Hkv=2, Sq=200, D=64, capacity=256, max_seqlen_k=256, num_splits=2,
-                         sq=SQ, so=SQ, sm_scale=0.125, q_qmax=127, causal=1, stream=None),
-    "lbfa_prefill_paged": dict(q=P, dtype=0, k_codes=P, k_scale=P, v_cache=P, km=P, seqlens=P, q_lens=None, block_table=P, slots=None,
-                               o=P, lse=None, workspace=P, workspace_bytes=WS, B=1, Hq=4, Hkv=2, Sq=200, D=64, num_slots=2,
-                               num_pages=8, page_size=128, max_pages=2, max_seqlen_k=256, num_splits=2, sq=SQ, so=SQ,
-                               sm_scale=0.125, q_qmax=127, causal=1, stream=None),
-}
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from lowbit_quant_fa2_paddle_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
-
-
-def call(lib, name, **overrides):
-    args = dict(DEFAULTS[name])
-    assert overrides and set(overrides) <= set(args), (name, overrides)
-    args.update(overrides)
-    st = getattr(lib, name)(*[cabi_calls._arg(v) for v in args.values()])
-    return st, lib.lbfa_last_error().decode()
 
 
 def test_new_symbols_are_exported_and_declared(lib):
@@ -102,7 +73,7 @@ SINGLE_FAULT = [
     ("lbfa_prefill_paged", dict(page_size=100), "lbfa_prefill_paged: page_size must be a positive multiple of 64, got 100"),
     ("lbfa_prefill_paged", dict(num_pages=0),
      "lbfa_prefill_paged: num_pages, num_slots and max_pages_per_seq must be at least 1, got 0, 2 and 2"),
-    ("lbfa_prefill_paged", dict(max_pages=1 << 25), "lbfa_prefill_paged: max_pages_per_seq * page_size must stay below 2^31 keys"),
+    ("lbfa_prefill_paged", dict(max_pages_per_seq=1 << 25), "lbfa_prefill_paged: max_pages_per_seq * page_size must stay below 2^31 keys"),
     ("lbfa_prefill_paged", dict(B=3), "lbfa_prefill_paged: B (3) exceeds num_slots (2)"),
     ("lbfa_prefill_paged", dict(max_seqlen_k=257),
      "lbfa_prefill_paged: max_seqlen_k must be in [1, max_pages_per_seq * page_size], got 257 (limit 256)"),
@@ -117,16 +88,11 @@ SINGLE_FAULT = [
 
 
 def test_single_fault_table(lib):
-    from lowbit_quant_fa2_paddle_amd import _lib
-    for name, overrides, message in SINGLE_FAULT:
-        st, msg = call(lib, name, **overrides)
-        assert st == _lib.LBFA_EINVAL, (name, overrides, st, msg)
-        assert msg == message, (name, overrides, msg)
+    check_table(lib, SINGLE_FAULT)
 
 
 def test_decode_still_refuses_long_queries(lib):
-    import test_decode_abi_cpu as dec
-    st, msg = dec.call(lib, "lbfa_decode", Sq=33)
+    st, msg = call(lib, "lbfa_decode", Sq=33)
     assert st == 1 and "the limit is 64" in msg
 
 
@@ -154,7 +120,7 @@ def test_the_call_uses_the_prefill_split_rule(lib):
     """num_splits = 0 inside the call is lbfa_prefill_num_splits, not decode's rule: one byte less than
     lbfa_prefill_workspace_bytes(..., 0) is refused with exactly that size (64 slices here; decode's rule would take 256)"""
     for name in ("lbfa_prefill", "lbfa_prefill_paged"):
-        kw = dict(capacity=65536) if name == "lbfa_prefill" else dict(page_size=8192, max_pages=8)
+        kw = dict(capacity=65536) if name == "lbfa_prefill" else dict(page_size=8192, max_pages_per_seq=8)
         assert lib.lbfa_prefill_num_splits(1, 4, 200, 65536) == 64 and lib.lbfa_decode_num_splits(1, 2, 65536) == 256
         need = lib.lbfa_prefill_workspace_bytes(1, 4, 2, 200, 64, 65536, 0)
         assert need == lib.lbfa_prefill_workspace_bytes(1, 4, 2, 200, 64, 65536, 64) > 0

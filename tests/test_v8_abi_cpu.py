@@ -6,50 +6,11 @@ import os
 
 import pytest
 
-import cabi_calls
-from cabi_calls import A, P, S3
+from cabi_calls import DEFAULTS, V8, A, P, call, check_table, lib  # noqa: F401 (lib: the fixture)
 
+# the default problems (cabi_calls.DEFAULTS) are the siblings' with v_scale behind v_cache
 NEW = ["lbfa_kvcache_append_v8", "lbfa_kvcache_paged_append_v8", "lbfa_decode_v8", "lbfa_decode_paged_v8", "lbfa_prefill_v8",
        "lbfa_prefill_paged_v8"]
-WS = 1 << 15
-_POOL = dict(num_slots=1, num_pages=2, page_size=64, max_pages=2)
-_Q = dict(sq=(2048, 512, 64), so=(2048, 512, 64), sm_scale=0.125, q_qmax=127, causal=0, stream=None)
-# name -> arguments in ABI order with the values of a small valid problem: B 1, Hkv 2, D 64, T / Sq 8, 128 keys of room
-DEFAULTS = {
-    "lbfa_kvcache_append_v8": dict(k_new=P, v_new=P, dtype=0, new_lens=None, km=P, k_codes=P, k_scale=P, v_cache=P, v_scale=P,
-                                   k_tail=P, seqlens=P, B=1, Hkv=2, T=8, D=64, capacity=128, sk=S3, sv=S3, k_qmax=127, stream=None),
-    "lbfa_kvcache_paged_append_v8": dict(k_new=P, v_new=P, dtype=0, new_lens=None, km=P, k_codes=P, k_scale=P, v_cache=P, v_scale=P,
-                                         k_tail=P, seqlens=P, block_table=P, slots=None, B=1, Hkv=2, T=8, D=64, **_POOL, sk=S3,
-                                         sv=S3, k_qmax=127, stream=None),
-    "lbfa_decode_v8": dict(q=P, dtype=0, k_codes=P, k_scale=P, v_cache=P, v_scale=P, km=P, seqlens=P, o=P, lse=None, workspace=P,
-                           workspace_bytes=WS, B=1, Hq=4, Hkv=2, Sq=8, D=64, capacity=128, max_seqlen_k=128, num_splits=2, **_Q),
-    "lbfa_decode_paged_v8": dict(q=P, dtype=0, k_codes=P, k_scale=P, v_cache=P, v_scale=P, km=P, seqlens=P, block_table=P,
-                                 slots=None, o=P, lse=None, workspace=P, workspace_bytes=WS, B=1, Hq=4, Hkv=2, Sq=8, D=64, **_POOL,
-                                 max_seqlen_k=128, num_splits=2, **_Q),
-    "lbfa_prefill_v8": dict(q=P, dtype=0, k_codes=P, k_scale=P, v_cache=P, v_scale=P, km=P, seqlens=P, q_lens=None, o=P, lse=None,
-                            workspace=P, workspace_bytes=WS, B=1, Hq=4, Hkv=2, Sq=8, D=64, capacity=128, max_seqlen_k=128,
-                            num_splits=2, **_Q),
-    "lbfa_prefill_paged_v8": dict(q=P, dtype=0, k_codes=P, k_scale=P, v_cache=P, v_scale=P, km=P, seqlens=P, q_lens=None,
-                                  block_table=P, slots=None, o=P, lse=None, workspace=P, workspace_bytes=WS, B=1, Hq=4, Hkv=2, Sq=8,
-                                  D=64, **_POOL, max_seqlen_k=128, num_splits=2, **_Q),
-}
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from lowbit_quant_fa2_paddle_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
-
-
-def call(lib, name, **overrides):
-    args = dict(DEFAULTS[name])
-    assert overrides and set(overrides) <= set(args), (name, overrides)
-    args.update(overrides)
-    st = getattr(lib, name)(*[cabi_calls._arg(v) for v in args.values()])
-    return st, lib.lbfa_last_error().decode()
 
 
 def test_new_symbols_are_exported_and_declared(lib):
@@ -91,20 +52,35 @@ def test_refusals(lib):
             ql = " / q_lens" if "prefill" in name else ""
             table.append((name, dict(v_cache=A(8)), f"{name}: cache tensors and km must be 16-byte aligned, k_scale / seqlens{ql}{bad} / lse "
                                                     "4-byte aligned"))
-            table.append((name, dict(workspace_bytes=16), f"{name}: workspace too small (16 < 17408)"))
+            need = 435200 if "prefill" in name else 17408  # pinned by the siblings' tables for the same problems
+            table.append((name, dict(workspace_bytes=16), f"{name}: workspace too small (16 < {need})"))
             table.append((name, dict(Hq=3), "num_qo_heads (3) must be divisible by num_kv_heads (2)"))
         if paged:
             table.append((name, dict(page_size=100), f"{name}: page_size must be a positive multiple of 64, got 100"))
         else:
             table.append((name, dict(capacity=100), f"{name}: capacity must be a positive multiple of 64, got 100"))
-    for name, overrides, message in table:
-        st, msg = call(lib, name, **overrides)
-        assert st == _lib.LBFA_EINVAL, (name, overrides, st, msg)
-        assert msg == message, (name, overrides, msg)
+    check_table(lib, table)
     st, msg = call(lib, "lbfa_decode_v8", Sq=33)
     assert st == _lib.LBFA_EINVAL and "the limit is 64" in msg  # decode keeps its row limit, prefill has none
     with pytest.raises(ValueError, match="v_scale must be 16-byte aligned"):
         _lib.check(call(lib, "lbfa_prefill_v8", v_scale=A(4))[0], lib)
+
+
+def test_every_refusal_of_a_sibling_is_the_twin_s(lib):
+    """Every row of the three SINGLE_FAULT tables whose entry point has a _v8 sibling, made against the sibling with a valid
+    v_scale: the same refusal, with only the name in front of the message changed (a prefix: `lbfa_decode_num_splits` inside a
+    message stays)."""
+    import test_decode_abi_cpu as dec
+    import test_paged_abi_cpu as paged
+    import test_prefill_abi_cpu as prefill
+    rows = [r for mod in (dec, paged, prefill) for r in mod.SINGLE_FAULT if r[0] in V8]
+    assert len(rows) == 176 and {r[0] for r in rows} == set(V8)
+    twins = []
+    for name, overrides, message in rows:
+        prefix = name + ": "
+        twins.append((name + "_v8", dict(overrides, v_scale=P),
+                      name + "_v8: " + message[len(prefix):] if message.startswith(prefix) else message))
+    check_table(lib, twins)
 
 
 def test_front_end_takes_v_bits():
