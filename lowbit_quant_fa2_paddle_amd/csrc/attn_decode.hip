@@ -29,6 +29,9 @@
 // table load for tile t) and locate(t, pg) (the number that names the tile to the loads).  Everything else - Q prologue, masks,
 // online softmax, V staging, epilogue, partials - is written once and does not know where a tile lives (the schedule of the
 // tile loop has a form with and one without table look-ups, see there): same products in the same order per slice, so the two layouts give bit-identical results for the same number of slices.
+// What happens to a tile - load_k / load_v / store_v / compute with the running state of the online softmax - is written once for
+// this kernel and for cached prefill (attn_prefill.hip), in attn_cache_tile.inc; the Q prologue, the tile loop and the epilogue are
+// this kernel's own (attn_decode_body.inc).
 #include "attn_common.h"
 #include "kv_policy.h"
 
@@ -37,7 +40,8 @@ namespace lbfa {
 // The body is written once, in attn_decode_body.inc, and included as text into both kernels: VB = bits of a cached V element, 16 (fp16) or 8
 // (e4m3 codes with a scale per key, kv_policy.h).  Text, not a function the two kernels call: routed through an inlined function
 // the fp16 instances compile to other code than they had (same instructions, another schedule), and they are the yardstick the fp8
-// family is measured against.  Included, they are the code they were, byte for byte.
+// family is measured against.  Included, they are the code they were, byte for byte.  The body includes attn_cache_tile.inc, the
+// text it shares with the prefill body, for the same reason.
 // The format is known to load_v and store_v only.
 template <class KV, int DT, int D, int MB>
 __global__ __launch_bounds__(64) void attn_decode_kernel(typename KV::Params p) {

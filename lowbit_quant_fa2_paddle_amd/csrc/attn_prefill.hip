@@ -1,7 +1,8 @@
 // Cached prefill: attention of ANY number of new queries to the int8 KV cache (kvcache.hip), contiguous or paged, gfx950.
 //
 // One workgroup = FOUR waves = one (batch, query head, 128-row Q block, key slice); each wave owns 32 query rows as two 16-row
-// blocks (the MB = 2 shape of attn_decode.hip), with that kernel's lane roles, MFMA shapes and tile arithmetic:
+// blocks (the MB = 2 shape of attn_decode.hip), with that kernel's lane roles, MFMA shapes and tile arithmetic - not a copy of it:
+// both bodies include the one text of it, attn_cache_tile.inc (running state, tile bases, load_k / load_v / store_v / compute):
 //   S^T = K Q^T  (v_mfma_i32_16x16x64_i8), s = fp32(int32(q . k)) * q_scale * k_scale, keys >= the row's limit -> -inf,
 //   online softmax in base 2 on the exact argument s - m, P rounded to fp16, O^T += V^T P^T (v_mfma_f32_16x16x32_f16, fp32
 //   accumulation), V read back transposed with ds_read_b64_tr_b16 from the [64][2 D + 32] image.
@@ -43,7 +44,9 @@ __device__ __forceinline__ int wave_min_i32(int v) {
 // The body is written once, in attn_prefill_body.inc, and included as text into both kernels: VB = bits of a cached V element, 16 (fp16) or 8
 // (e4m3 codes with a scale per key, kv_policy.h).  Text, not a function the two kernels call: routed through an inlined function
 // the fp16 instances compile to other code than they had (same instructions, another schedule), and they are the yardstick the fp8
-// family is measured against.  Included, they are the code they were, byte for byte.
+// family is measured against.  Included, they are the code they were, byte for byte.  The body includes attn_cache_tile.inc, the
+// text it shares with the decode body: a V tile belongs to the 256 threads here (NT, tix), the Q scale is the block's, and a tile
+// below every row limit of the wave calls compute without the key-limit compare.
 // The format is known to load_v and store_v only.
 template <class KV, int DT, int D>
 __global__ __launch_bounds__(256) void attn_prefill_kernel(typename PrefillOf<KV>::type p) {

@@ -77,115 +77,11 @@
   // the compare against the row limits is needed only in tiles that reach past the smallest limit of this wave's rows
   const int lim_min = wave_min_i32(min(lim[0], lim[1]));
 
-  // ---- running state ---------------------------------------------------------------------------------------------------
-  f32x4 acc[MB][CB];
-  float m_run[MB], l_run[MB];
-#pragma unroll
-  for (int rb = 0; rb < MB; ++rb) {
-    m_run[rb] = -__builtin_inff();
-    l_run[rb] = 0.f;
-#pragma unroll
-    for (int cb = 0; cb < CB; ++cb) acc[rb][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-
-  const int8_t* kbase = kv.codes + (int64_t)i16 * D + 16 * g;
-  const unsigned short* vbase = kv.v;
-  const float* ksc = kv.scale;
-  typedef __attribute__((address_space(3))) unsigned char lds_byte;
-  typedef __attribute__((address_space(3))) s16x4v lds_s16x4;
-  lds_byte* const vt_lane = (lds_byte*)smem + (4 * g + (i16 >> 2)) * VROW + (i16 & 3) * 8;
-
-  auto load_k = [&](tile_t t, i32x4 (&kf)[4][KS]) __attribute__((always_inline)) {
-    const int8_t* kt = kbase + (int64_t)t * 64 * D;
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-      for (int s = 0; s < KS; ++s) kf[kb][s] = *reinterpret_cast<const i32x4*>(kt + kb * 16 * D + 64 * s);
-  };
-  const uint8_t* v8base = nullptr;  // fp8 V: the codes and the scales of (b, hk), or of the pool
-  const float* vsbase = nullptr;
-  if constexpr (VB == 8) {
-    const int64_t key0 = KV::key0(p, b, hk);
-    v8base = reinterpret_cast<const uint8_t*>(p.v) + key0 * D;
-    vsbase = p.v_scale + key0;
-  }
-  auto load_v = [&](tile_t t, vstage_t& vr) __attribute__((always_inline)) {
-    if constexpr (VB == 8) {
-      const uint8_t* vt = v8base + (int64_t)t * 64 * D;
-#pragma unroll
-      for (int u = 0; u < VCH; ++u) load_v8_chunk<D>(vt, vsbase + (int64_t)t * 64, u * 256 + tid, vr.c[u], vr.s[u]);
-    } else {
-      const unsigned short* vt = vbase + (int64_t)t * 64 * D;
-#pragma unroll
-      for (int u = 0; u < VCH; ++u) vr.c[u] = *reinterpret_cast<const uint4*>(vt + (u * 256 + tid) * 8);  // the tile is contiguous
-    }
-  };
-  auto store_v = [&](int t, const vstage_t& vr) __attribute__((always_inline)) {
-#pragma unroll
-    for (int u = 0; u < VCH; ++u) {
-      if constexpr (VB == 8) {
-        store_vhat_chunk<D, VROW>(smem, u * 256 + tid, vr.c[u], vr.s[u], n - t * 64);
-      } else {
-        const int cidx = u * 256 + tid, r = cidx / (D / 8), ch = cidx % (D / 8);
-        // rows past the end may hold anything (0 * NaN): they enter the product as zeros
-        const uint4 val = (t * 64 + r < n) ? vr.c[u] : make_uint4(0, 0, 0, 0);
-        *reinterpret_cast<uint4*>(smem + r * VROW + ch * 16) = val;
-      }
-    }
-  };
-  auto compute = [&](int t, tile_t gt, const i32x4 (&kf)[4][KS], auto masked) __attribute__((always_inline)) {
-    constexpr bool MASK = decltype(masked)::value;
-    const float kscale = ksc[gt];
-#pragma unroll
-    for (int rb = 0; rb < MB; ++rb) {
-      float sc[4][4];
-      float tmax = -__builtin_inff();
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) {
-        i32x4 sacc = i32x4{0, 0, 0, 0};
-#pragma unroll
-        for (int s = 0; s < KS; ++s) sacc = __builtin_amdgcn_mfma_i32_16x16x64_i8(kf[kb][s], qf[rb][s], sacc, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float s2 = (float)sacc[r] * qsc * kscale;
-          if constexpr (MASK) s2 = t * 64 + kb * 16 + 4 * g + r < lim[rb] ? s2 : -__builtin_inff();
-          sc[kb][r] = s2;
-          tmax = fmaxf(tmax, s2);
-        }
-      }
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-      const float m_new = fmaxf(m_run[rb], tmax);
-      const float m_use = m_new == -__builtin_inff() ? 0.f : m_new;  // a row with no visible key yet: p = 0, no NaN
-      const float alpha = __builtin_amdgcn_exp2f(m_run[rb] - m_use);
-      float lsum = 0.f;
-      f16x8 pf[2];
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float pe = __builtin_amdgcn_exp2f(sc[kb][r] - m_use);
-          lsum += pe;
-          pf[kb >> 1][(kb & 1) * 4 + r] = (_Float16)pe;
-        }
-      lsum += __shfl_xor(lsum, 16, 64);
-      lsum += __shfl_xor(lsum, 32, 64);
-      l_run[rb] = l_run[rb] * alpha + lsum;
-      m_run[rb] = m_new;
-#pragma unroll
-      for (int cb = 0; cb < CB; ++cb) {
-        acc[rb][cb] *= alpha;
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          const s16x4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vt_lane + (32 * s) * VROW + cb * 32));
-          const s16x4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vt_lane + (32 * s + 16) * VROW + cb * 32));
-          const f16x4 lo16 = __builtin_bit_cast(f16x4, lo), hi16 = __builtin_bit_cast(f16x4, hi);
-          const f16x8 vf = f16x8{lo16[0], lo16[1], lo16[2], lo16[3], hi16[0], hi16[1], hi16[2], hi16[3]};
-          acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pf[s], acc[rb][cb], 0, 0, 0);
-        }
-      }
-    }
-  };
+  // ---- the tile: running state, bases, load_k / load_v / store_v / compute, shared with the decode body --------------------------
+  constexpr int NT = 256;  // a V tile belongs to the four waves
+  const int tix = tid;
+  auto q_scale = [&](int) __attribute__((always_inline)) { return qsc; };  // one block of 128 rows: the workgroup's
+#include "attn_cache_tile.inc"
   // wave-uniform: a tile wholly below every limit of the wave's rows takes the form without the compare (same bits)
   auto tile = [&](int t, tile_t gt, const i32x4 (&kf)[4][KS]) __attribute__((always_inline)) {
     if (t * 64 + 64 <= lim_min) compute(t, gt, kf, std::false_type{});

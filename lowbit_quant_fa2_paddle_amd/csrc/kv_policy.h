@@ -1,5 +1,6 @@
 // Where a 64-key tile of the int8 KV cache lives: the policies the kernels that read the cache (attn_decode.hip,
-// attn_prefill.hip) are instantiated with - one kernel body each for the contiguous cache and for the paged one.
+// attn_prefill.hip) are instantiated with - one kernel body each for the contiguous cache and for the paged one, and one text of
+// what both do with a tile (attn_cache_tile.inc).
 #pragma once
 #include "attn_common.h"
 
@@ -103,7 +104,8 @@ __device__ __forceinline__ void e4m3x16_to_vhat(const uint4& codes, float scale,
 }
 
 // A tile of the fp8 V cache is 64 D contiguous code bytes and 64 contiguous scales; chunk `cidx` of it is 16 channels of key
-// cidx / (D / 16).  The two steps of a reader, shared by the decode and the prefill body (their threads differ in which chunks they take):
+// cidx / (D / 16).  The two steps of a reader, called by load_v / store_v of attn_cache_tile.inc (thread tix of the NT that share the tile
+// takes chunks u * NT + tix):
 // fetch a chunk with the scale of its key ...
 template <int D>
 __device__ __forceinline__ void load_v8_chunk(const uint8_t* tile, const float* scales, int cidx, uint4& codes, float& scale) {

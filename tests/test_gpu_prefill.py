@@ -8,7 +8,8 @@ int8 KV cache.
   pool full of garbage, a `slots` permutation) against the contiguous one;
 * chunked == one-shot, bit for bit with one slice;
 * the golden fixtures of the reference's kernels, through a cache filled by one append;
-* at M <= 64 prefill and decode both meet the bound of the same oracle output.
+* at M <= 64 prefill and decode both meet the bound of the same oracle output, and - non-causal, the same explicit num_splits -
+  equal each other bit for bit.
 """
 import numpy as np
 import pytest
@@ -247,6 +248,32 @@ def test_short_queries_prefill_and_decode_meet_the_same_oracle(oracle, dev, case
                 o, lse = fn(tq, cache, tensor_layout=layout, is_causal=causal, return_lse=True, num_splits=ns)
                 kr.check_o(_np(o if layout == "HND" else o.transpose(1, 2)), o_ref[..., :D], dtype, what)
                 kr.check_lse(lse.cpu().numpy(), lse_ref, c["corr"], c["sm_scale"], dtype, what)
+
+
+@pytest.mark.parametrize("v_bits", [16, 8])
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+@pytest.mark.parametrize("D", [64, 128])
+def test_short_queries_prefill_equals_decode_bit_for_bit(oracle, dev, D, dtype, v_bits):
+    """Where both operators take the call - non-causal, M = Sq * G <= 64, q_lens full - they are the same computation: one Q block
+    per query head with the same amax, the tile arithmetic both kernels take from one text (csrc/attn_cache_tile.inc), and, for the
+    same explicit num_splits, the same slices of the same four tiles (n = 200: the last one ragged; with 3 slices the third is
+    empty) added by the same combine kernel.  Sq 1 / 16 / 32 at G = 2 are the three row-block counts of decode (M = 2, 32, 64)."""
+    import lowbit_quant_fa2_paddle_amd as lb
+    hkv, grp, n = 2, 2, 200
+    rng = np.random.default_rng(1000 * D + v_bits)
+    mk = lambda h, rows, bias: _t(oracle.to_storage(rng.standard_normal((B, h, rows, D), dtype=np.float32) + np.float32(bias), dtype),
+                                  dtype, dev)
+    cache = lb.LowbitKVCache(B, hkv, D, 256, TDT[dtype], dev, v_bits=v_bits).append(mk(hkv, n, 0.5), mk(hkv, n, 0.0))
+    for Sq in (1, 16, 32):
+        q = mk(hkv * grp, Sq, 0.0)
+        for ns in (1, 3):
+            what = f"D={D} {dtype} v_bits={v_bits} Sq={Sq} splits={ns}"
+            o, lse = lb.lowbit_fa_prefill(q, cache, return_lse=True, num_splits=ns)
+            od, ld = lb.lowbit_fa_decode(q, cache, return_lse=True, num_splits=ns)
+            assert torch.isfinite(o.float()).all() and torch.isfinite(lse).all(), what
+            for name, x, y in (("O", o, od), ("LSE", lse, ld)):
+                bad = torch.nonzero(x != y)
+                assert torch.equal(x, y), f"{what}: {name} differs in {len(bad)} elements, the first at {bad[0].tolist()}"
 
 
 def test_front_end_refusals(dev):

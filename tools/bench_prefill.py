@@ -141,10 +141,11 @@ def _oracle_references(D, Sq, n, causal):
     ref = v8.CacheRefV8(orc, 1, hkv, D, (n + 63) // 64 * 64, "fp16")  # the K state and the fp16 V are CacheRef's
     ref.append(k, v)
     q_i8, q_scale = pr.quant_q_blocks(orc, q, [Sq], sm, 127)
-    want = {"prefill": pr.oracle_prefill(orc, q_i8, q_scale, ref, [Sq], causal=causal, out_dtype="fp16")[0]}
+    # (oracle_prefill reads V^ of a CacheRefV8: the fp16 arms get the same K state with the fp16 V)
+    ref16 = types.SimpleNamespace(k_codes=ref.k_codes, k_scale=ref.k_scale, v=ref.v, seqlens=ref.seqlens)
+    want = {"prefill": pr.oracle_prefill(orc, q_i8, q_scale, ref16, [Sq], causal=causal, out_dtype="fp16")[0]}
     want["prefill_1"] = want["prefill"]
-    ref_hat = types.SimpleNamespace(k_codes=ref.k_codes, k_scale=ref.k_scale, v=ref.vhat(), seqlens=ref.seqlens)
-    want["prefill_v8"] = pr.oracle_prefill(orc, q_i8, q_scale, ref_hat, [Sq], causal=causal, out_dtype="fp16")[0]
+    want["prefill_v8"] = pr.oracle_prefill(orc, q_i8, q_scale, ref, [Sq], causal=causal, out_dtype="fp16")[0]
     want["dense_int8"] = orc.lowbit_fa_forward(q, k, v, is_causal=False, tail="neg_inf", amax_floor=1e-7)
     if causal and Sq == n:
         want["dense_causal"] = orc.lowbit_fa_forward(q, k, v, is_causal=True, tail="neg_inf", amax_floor=1e-7)
