@@ -543,6 +543,86 @@ int lbfa_prefill_paged_v8(const void* q, int dtype, const int8_t* k_codes, const
                           int max_pages_per_seq, int max_seqlen_k, int num_splits, const int64_t strides_q[3],
                           const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream);
 
+/* ---- nibble-packed int4 K cache: two K codes per byte (additive to ABI 200) -----------------------------------------------
+ * With k_qmax = 7 the K codes lie in [-7, 7] and still take a byte each in the caches above: as large, as long a stream as int8
+ * codes.  The _k4 entry points keep them two to a byte, D / 2 bytes per key and kv head: the decode stream is 2.5 D bytes per key
+ * instead of 3 D with fp16 V (_k4), 1.5 D + 4 instead of 2 D + 4 with fp8 V (_k4_v8).
+ *
+ * Format.  k_codes is uint8 [B, Hkv, capacity, D / 2] (paged: [num_pages, Hkv, page_size, D / 2]).  Byte j of a row holds channel
+ * 2 j in bits 0..3 and channel 2 j + 1 in bits 4..7, each nibble the two's-complement 4-bit value of the code the byte cache would
+ * hold; the quantiser never produces -8.  A 64-key tile is 32 D contiguous bytes inside one page.  k_scale, k_tail, km, seqlens,
+ * v_cache, v_scale, the block table and the re-quantisation of the open 64-key block on each append are exactly the byte cache's: a
+ * row is packed from its own codes, so any append schedule gives the state of a one-shot append, bit for bit, and the codes are
+ * those of the sibling called with k_qmax = 7.
+ *
+ * A read of a packed cache equals, bit for bit, the same read of the byte-per-code cache with k_qmax = 7, for the same num_splits,
+ * contiguous or paged: the integer score q . k does not depend on the order its channels are added in, and everything behind it
+ * is the sibling's kernel.
+ *
+ * Each entry point has the contract, the refusals and the device-side defences of its sibling without "_k4" (lengths clamped;
+ * slot and page ids clamped for the reads and skipped for the appends; appends clipped at the capacity), the same split rules and
+ * workspace sizes, and the sibling's argument list with k_codes as uint8_t*.  One more refusal, LBFA_EINVAL before any launch: an
+ * append with k_qmax != 7 ("k_qmax must be 7 ..."): the codes must fit a nibble.  k_codes must be 16-byte aligned, as the
+ * siblings' (their message).
+ */
+int lbfa_kvcache_append_k4(const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
+                           uint8_t* k_codes, float* k_scale, void* v_cache, void* k_tail, const int32_t* seqlens,
+                           int B, int Hkv, int T, int D, int capacity, const int64_t strides_k[3], const int64_t strides_v[3],
+                           int k_qmax, void* stream);
+int lbfa_kvcache_paged_append_k4(const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
+                                 uint8_t* k_codes, float* k_scale, void* v_cache, void* k_tail, const int32_t* seqlens,
+                                 const int32_t* block_table, const int32_t* slots, int B, int Hkv, int T, int D, int num_slots,
+                                 int num_pages, int page_size, int max_pages_per_seq, const int64_t strides_k[3],
+                                 const int64_t strides_v[3], int k_qmax, void* stream);
+int lbfa_kvcache_append_k4_v8(const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
+                              uint8_t* k_codes, float* k_scale, uint8_t* v_cache, float* v_scale, void* k_tail, const int32_t* seqlens,
+                              int B, int Hkv, int T, int D, int capacity, const int64_t strides_k[3], const int64_t strides_v[3],
+                              int k_qmax, void* stream);
+int lbfa_kvcache_paged_append_k4_v8(const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
+                                    uint8_t* k_codes, float* k_scale, uint8_t* v_cache, float* v_scale, void* k_tail,
+                                    const int32_t* seqlens, const int32_t* block_table, const int32_t* slots, int B, int Hkv, int T,
+                                    int D, int num_slots, int num_pages, int page_size, int max_pages_per_seq,
+                                    const int64_t strides_k[3], const int64_t strides_v[3], int k_qmax, void* stream);
+int lbfa_decode_k4(const void* q, int dtype, const uint8_t* k_codes, const float* k_scale, const void* v_cache, const void* km,
+                   const int32_t* seqlens, void* o, float* lse, void* workspace, size_t workspace_bytes,
+                   int B, int Hq, int Hkv, int Sq, int D, int capacity, int max_seqlen_k, int num_splits,
+                   const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream);
+int lbfa_decode_paged_k4(const void* q, int dtype, const uint8_t* k_codes, const float* k_scale, const void* v_cache, const void* km,
+                         const int32_t* seqlens, const int32_t* block_table, const int32_t* slots, void* o, float* lse,
+                         void* workspace, size_t workspace_bytes, int B, int Hq, int Hkv, int Sq, int D, int num_slots, int num_pages,
+                         int page_size, int max_pages_per_seq, int max_seqlen_k, int num_splits, const int64_t strides_q[3],
+                         const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream);
+int lbfa_decode_k4_v8(const void* q, int dtype, const uint8_t* k_codes, const float* k_scale, const uint8_t* v_cache, const float* v_scale,
+                      const void* km, const int32_t* seqlens, void* o, float* lse, void* workspace, size_t workspace_bytes,
+                      int B, int Hq, int Hkv, int Sq, int D, int capacity, int max_seqlen_k, int num_splits,
+                      const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream);
+int lbfa_decode_paged_k4_v8(const void* q, int dtype, const uint8_t* k_codes, const float* k_scale, const uint8_t* v_cache,
+                            const float* v_scale, const void* km, const int32_t* seqlens, const int32_t* block_table,
+                            const int32_t* slots, void* o, float* lse, void* workspace, size_t workspace_bytes, int B, int Hq, int Hkv,
+                            int Sq, int D, int num_slots, int num_pages, int page_size, int max_pages_per_seq, int max_seqlen_k,
+                            int num_splits, const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax,
+                            int is_causal, void* stream);
+int lbfa_prefill_k4(const void* q, int dtype, const uint8_t* k_codes, const float* k_scale, const void* v_cache, const void* km,
+                    const int32_t* seqlens, const int32_t* q_lens, void* o, float* lse, void* workspace, size_t workspace_bytes,
+                    int B, int Hq, int Hkv, int Sq, int D, int capacity, int max_seqlen_k, int num_splits,
+                    const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream);
+int lbfa_prefill_paged_k4(const void* q, int dtype, const uint8_t* k_codes, const float* k_scale, const void* v_cache, const void* km,
+                          const int32_t* seqlens, const int32_t* q_lens, const int32_t* block_table, const int32_t* slots, void* o,
+                          float* lse, void* workspace, size_t workspace_bytes, int B, int Hq, int Hkv, int Sq, int D, int num_slots,
+                          int num_pages, int page_size, int max_pages_per_seq, int max_seqlen_k, int num_splits,
+                          const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal,
+                          void* stream);
+int lbfa_prefill_k4_v8(const void* q, int dtype, const uint8_t* k_codes, const float* k_scale, const uint8_t* v_cache, const float* v_scale,
+                       const void* km, const int32_t* seqlens, const int32_t* q_lens, void* o, float* lse, void* workspace,
+                       size_t workspace_bytes, int B, int Hq, int Hkv, int Sq, int D, int capacity, int max_seqlen_k, int num_splits,
+                       const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream);
+int lbfa_prefill_paged_k4_v8(const void* q, int dtype, const uint8_t* k_codes, const float* k_scale, const uint8_t* v_cache,
+                             const float* v_scale, const void* km, const int32_t* seqlens, const int32_t* q_lens,
+                             const int32_t* block_table, const int32_t* slots, void* o, float* lse, void* workspace,
+                             size_t workspace_bytes, int B, int Hq, int Hkv, int Sq, int D, int num_slots, int num_pages, int page_size,
+                             int max_pages_per_seq, int max_seqlen_k, int num_splits, const int64_t strides_q[3],
+                             const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

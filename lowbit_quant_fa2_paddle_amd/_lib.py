@@ -99,6 +99,10 @@ for _name, _at in (("lbfa_kvcache_append", 8), ("lbfa_kvcache_paged_append", 8),
                    ("lbfa_prefill", 5), ("lbfa_prefill_paged", 5)):
     _res, _args = SIGNATURES[_name]
     SIGNATURES[_name + "_v8"] = (_res, _args[:_at] + [_vp] + _args[_at:])
+# the nibble-packed K cache: each of the twelve once more, the sibling's argument list with k_codes two codes per byte
+for _name in ("lbfa_kvcache_append", "lbfa_kvcache_paged_append", "lbfa_decode", "lbfa_decode_paged", "lbfa_prefill", "lbfa_prefill_paged"):
+    SIGNATURES[_name + "_k4"] = SIGNATURES[_name]
+    SIGNATURES[_name + "_k4_v8"] = SIGNATURES[_name + "_v8"]
 
 _lock = threading.Lock()
 _lib = None

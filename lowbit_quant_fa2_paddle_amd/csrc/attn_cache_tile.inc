@@ -1,8 +1,8 @@
 // What a reader of the KV cache does with one 64-key tile, written once: the running state of the online softmax, the bases of a
 // tile, and load_k / load_v / store_v / compute.  Included as text by attn_decode_body.inc and attn_prefill_body.inc (text for the
 // reason attn_decode.hip gives), after the Q prologue and in front of the tile loop.  The including body has in scope:
-//   the kernel's D, VB, KV, p;  MB, KS, CB, VROW, VCH, vstage_t, tile_t, smem;  kv, n, b, hk, lane roles i16, g;
-//   qf[MB][KS] (the Q codes) and lim[MB] (first key a row does NOT see);
+//   the kernel's D, VB, KB, KV, p;  MB, KS, CB, VROW, VCH, vstage_t, kfrag_t, tile_t, smem;  kv, n, b, hk, lane roles i16, g;
+//   qf[MB][KS] (the Q codes; packed K: in the channel order of k4_widen) and lim[MB] (first key a row does NOT see);
 //   NT, tix     the NT threads (64: a wave, 256: the workgroup) that share a V tile, and this thread's index among them: thread tix
 //               takes the 16-byte chunks u * NT + tix, u < VCH, of the tile;
 //   q_scale(rb) the Q scale of row block rb.
@@ -10,6 +10,10 @@
 // compare, std::false_type{} is for a tile wholly below every limit (same bits).
 // The three score statements - name the key, form the product, then the compare - stay in this order and as three statements:
 // folded or re-ordered they are the same arithmetic, but the compiler schedules every decode instance differently.
+// KB = bits of a cached K code.  8: a lane's 16 codes of a key are 16 bytes, the MFMA operand as it is loaded.  4 (the packed
+// cache, kv_policy.h): they are 8 bytes, a tile stays packed in its registers (kfrag_t: half of them) until compute widens it, and
+// the score accumulator holds 16 times the byte cache's integer, shifted back before the conversion.  Known to load_k and to the
+// score product only; everything from `(float)sacc` on is one text.
   f32x4 acc[MB][CB];
   float m_run[MB], l_run[MB];
 #pragma unroll
@@ -21,18 +25,28 @@
   }
 
   const int8_t* kbase = kv.codes + (int64_t)i16 * D + 16 * g;
+  const int8_t* k4base = nullptr;  // packed K: rows of D / 2 bytes behind the first key of (b, hk), or of the pool
+  if constexpr (KB == 4) k4base = p.k_codes + (KV::key0(p, b, hk) + i16) * (D / 2) + 8 * g;
   const unsigned short* vbase = kv.v;
   const float* ksc = kv.scale;
   typedef __attribute__((address_space(3))) unsigned char lds_byte;
   typedef __attribute__((address_space(3))) s16x4v lds_s16x4;
   lds_byte* const vt_lane = (lds_byte*)smem + (4 * g + (i16 >> 2)) * VROW + (i16 & 3) * 8;
 
-  auto load_k = [&](tile_t t, i32x4 (&kf)[4][KS]) __attribute__((always_inline)) {
-    const int8_t* kt = kbase + (int64_t)t * 64 * D;
+  auto load_k = [&](tile_t t, kfrag_t (&kf)[4][KS]) __attribute__((always_inline)) {
+    if constexpr (KB == 4) {
+      const int8_t* kt = k4base + (int64_t)t * 32 * D;
 #pragma unroll
-    for (int kb = 0; kb < 4; ++kb)
+      for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
-      for (int s = 0; s < KS; ++s) kf[kb][s] = *reinterpret_cast<const i32x4*>(kt + kb * 16 * D + 64 * s);
+        for (int s = 0; s < KS; ++s) kf[kb][s] = *reinterpret_cast<const u32x2*>(kt + kb * 8 * D + 32 * s);
+    } else {
+      const int8_t* kt = kbase + (int64_t)t * 64 * D;
+#pragma unroll
+      for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+        for (int s = 0; s < KS; ++s) kf[kb][s] = *reinterpret_cast<const i32x4*>(kt + kb * 16 * D + 64 * s);
+    }
   };
   const uint8_t* v8base = nullptr;  // fp8 V: the codes and the scales of (b, hk), or of the pool
   const float* vsbase = nullptr;
@@ -65,7 +79,7 @@
       }
     }
   };
-  auto compute = [&](int t, tile_t gt, const i32x4 (&kf)[4][KS], auto masked) __attribute__((always_inline)) {
+  auto compute = [&](int t, tile_t gt, const kfrag_t (&kf)[4][KS], auto masked) __attribute__((always_inline)) {
     constexpr bool MASK = decltype(masked)::value;
     const float kscale = ksc[gt];
 #pragma unroll
@@ -76,7 +90,11 @@
       for (int kb = 0; kb < 4; ++kb) {
         i32x4 sacc = i32x4{0, 0, 0, 0};
 #pragma unroll
-        for (int s = 0; s < KS; ++s) sacc = __builtin_amdgcn_mfma_i32_16x16x64_i8(kf[kb][s], qf[rb][s], sacc, 0, 0, 0);
+        for (int s = 0; s < KS; ++s) {
+          if constexpr (KB == 4) sacc = __builtin_amdgcn_mfma_i32_16x16x64_i8(k4_widen(kf[kb][s]), qf[rb][s], sacc, 0, 0, 0);
+          else sacc = __builtin_amdgcn_mfma_i32_16x16x64_i8(kf[kb][s], qf[rb][s], sacc, 0, 0, 0);
+        }
+        if constexpr (KB == 4) sacc = sacc >> 4;  // 16 (q . k), exactly: the byte cache's integer
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int key = t * 64 + kb * 16 + 4 * g + r;

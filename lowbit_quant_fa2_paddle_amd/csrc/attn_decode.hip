@@ -42,18 +42,31 @@ namespace lbfa {
 // the fp16 instances compile to other code than they had (same instructions, another schedule), and they are the yardstick the fp8
 // family is measured against.  Included, they are the code they were, byte for byte.  The body includes attn_cache_tile.inc, the
 // text it shares with the prefill body, for the same reason.
-// The format is known to load_v and store_v only.
+// The V format is known to load_v and store_v only; KB = bits of a cached K code, known to load_k and the score product only.
 template <class KV, int DT, int D, int MB>
 __global__ __launch_bounds__(64) void attn_decode_kernel(typename KV::Params p) {
-  constexpr int VB = 16;
+  constexpr int VB = 16, KB = 8;
 #include "attn_decode_body.inc"
 }
 // the same kernel over the fp8 V cache; the name keeps its family apart from the fp16 one in the code object
 template <class KV, int DT, int D, int MB>
 __global__ __launch_bounds__(64) void attn_decode_v8_kernel(V8Params<typename KV::Params, const float*> p) {
-  constexpr int VB = 8;
+  constexpr int VB = 8, KB = 8;
 #include "attn_decode_body.inc"
 }
+// the same two kernels over the nibble-packed K cache (K4Params, lbfa_common.h): half the K bytes per key, widened in registers
+template <class KV, int DT, int D, int MB>
+__global__ __launch_bounds__(64) void attn_decode_k4_kernel(K4Params<typename KV::Params> p) {
+  constexpr int VB = 16, KB = 4;
+#include "attn_decode_body.inc"
+}
+template <class KV, int DT, int D, int MB>
+__global__ __launch_bounds__(64) void attn_decode_k4_v8_kernel(K4Params<V8Params<typename KV::Params, const float*>> p) {
+  constexpr int VB = 8, KB = 4;
+#include "attn_decode_body.inc"
+}
+
+#ifndef LBFA_K4_UNIT  // the combine kernel lives in the unit of the byte-per-code instances
 
 // Adds the slices of one query row: m = max m_s, l = sum l_s 2^(m_s - m), O = sum acc_s 2^(m_s - m) / l, in ONE fixed order - the
 // 256 threads are 256 / D groups of one thread per channel, group g adds its contiguous run of ceil(splits / groups) slices in
@@ -131,18 +144,23 @@ hipError_t launch_attn_decode_combine(const DecodeParams& p, int dtype, int D, h
   return hipGetLastError();
 }
 
+#endif  // LBFA_K4_UNIT
+
 // ---- host-side launchers (called from lbfa_api.hip) ----------------------------------------------------------------------
-// One launcher for the four decodes: the KV policy and the V format are the block's (CacheBlock, lbfa_common.h).
+// One launcher for the eight decodes: the KV policy and the formats of K and V are the block's (CacheBlock, lbfa_common.h).  The
+// file is compiled twice: as it is for the byte-per-code blocks, with LBFA_K4_UNIT for the packed-K ones.
 template <class P>
 hipError_t launch_decode(const P& p, int dtype, int D, hipStream_t stream) {
   static_assert(CacheBlock<P>::op == CacheOp::kDecode, "not a parameter block of the decode kernels");
   using KV = std::conditional_t<CacheBlock<P>::paged, PagedKV, ContiguousKV>;
-  constexpr int VB = CacheBlock<P>::v_bits;
+  constexpr int VB = CacheBlock<P>::v_bits, KB = CacheBlock<P>::k_bits;
   dim3 grid(p.splits, p.Hkv, p.B);
   const int mb = (p.M + 15) / 16;
 #define LBFA_DEC(DT, DD, MB)                                                                                       \
   do {                                                                                                             \
-    if constexpr (VB == 8) hipLaunchKernelGGL((attn_decode_v8_kernel<KV, DT, DD, MB>), grid, dim3(64), 0, stream, p); \
+    if constexpr (KB == 4 && VB == 8) hipLaunchKernelGGL((attn_decode_k4_v8_kernel<KV, DT, DD, MB>), grid, dim3(64), 0, stream, p); \
+    else if constexpr (KB == 4) hipLaunchKernelGGL((attn_decode_k4_kernel<KV, DT, DD, MB>), grid, dim3(64), 0, stream, p); \
+    else if constexpr (VB == 8) hipLaunchKernelGGL((attn_decode_v8_kernel<KV, DT, DD, MB>), grid, dim3(64), 0, stream, p); \
     else hipLaunchKernelGGL((attn_decode_kernel<KV, DT, DD, MB>), grid, dim3(64), 0, stream, p);                   \
   } while (0)
 #define LBFA_DEC1(DT, DD)                 \
@@ -159,9 +177,16 @@ hipError_t launch_decode(const P& p, int dtype, int D, hipStream_t stream) {
   if (e != hipSuccess || p.splits == 1) return e;
   return launch_attn_decode_combine(p, dtype, D, stream);  // the partials are indexed by row of the call: nothing paged in them
 }
+#ifndef LBFA_K4_UNIT
 template hipError_t launch_decode(const DecodeParams&, int, int, hipStream_t);
 template hipError_t launch_decode(const PagedDecodeParams&, int, int, hipStream_t);
 template hipError_t launch_decode(const V8Params<DecodeParams, const float*>&, int, int, hipStream_t);
 template hipError_t launch_decode(const V8Params<PagedDecodeParams, const float*>&, int, int, hipStream_t);
+#else
+template hipError_t launch_decode(const K4Params<DecodeParams>&, int, int, hipStream_t);
+template hipError_t launch_decode(const K4Params<PagedDecodeParams>&, int, int, hipStream_t);
+template hipError_t launch_decode(const K4Params<V8Params<DecodeParams, const float*>>&, int, int, hipStream_t);
+template hipError_t launch_decode(const K4Params<V8Params<PagedDecodeParams, const float*>>&, int, int, hipStream_t);
+#endif
 
 }  // namespace lbfa

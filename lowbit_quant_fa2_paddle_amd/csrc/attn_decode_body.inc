@@ -1,10 +1,12 @@
 // Body of attn_decode_kernel / attn_decode_v8_kernel (attn_decode.hip), included as text inside each with the kernel's template parameters, its parameter
-// block `p` and `constexpr int VB` (bits of a cached V element: 16 or 8) in scope.  See attn_decode.hip.
+// block `p`, `constexpr int VB` (bits of a cached V element: 16 or 8) and `constexpr int KB` (bits of a cached K code: 8, or 4 for the
+// nibble-packed cache) in scope.  See attn_decode.hip.
   constexpr int KS = D / 64;        // k-steps of the score product
   constexpr int CB = D / 16;        // 16-channel blocks of O^T
   constexpr int VROW = 2 * D + 32;  // bytes per LDS row
   constexpr int VCH = D * VB / 128;  // 16-byte chunks of a V tile per lane
   typedef VStage<VCH, VB == 8 ? VCH : 0> vstage_t;  // fp8 V: and the scale of each chunk's key
+  typedef std::conditional_t<KB == 4, u32x2, i32x4> kfrag_t;  // a lane's 16 codes of one key as they are loaded
   typedef typename KV::tile_t tile_t;
   __shared__ __attribute__((aligned(16))) unsigned char smem[64 * VROW];
   const int split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
@@ -77,7 +79,10 @@
       const float scale = block_scale(am, p.q_qmax);
       qsc[rb] = scale;
 #pragma unroll
-      for (int s = 0; s < KS; ++s) qf[rb][s] = quant_codes16<false>(xq[rb][s], scale, 0.f);  // the plain division
+      for (int s = 0; s < KS; ++s) {
+        qf[rb][s] = quant_codes16<false>(xq[rb][s], scale, 0.f);  // the plain division
+        if constexpr (KB == 4) qf[rb][s] = k4_q_order(qf[rb][s]);
+      }
     }
     __syncthreads();  // srow is dead: the memory becomes the V tile
   }
@@ -100,7 +105,7 @@
   if constexpr (!KV::kTable) {
     if constexpr (AHEAD) {
       if (t0 < t1) {
-        i32x4 ka[4][KS], kb_[4][KS];
+        kfrag_t ka[4][KS], kb_[4][KS];
         vstage_t vr;
         load_k(t0, ka);
         load_v(t0, vr);
@@ -126,7 +131,7 @@
       }
     } else {
       for (int t = t0; t < t1; ++t) {
-        i32x4 ka[4][KS];
+        kfrag_t ka[4][KS];
         vstage_t vr;
         load_k(t, ka);
         load_v(t, vr);
@@ -139,7 +144,7 @@
   } else {
     if constexpr (AHEAD) {
       if (t0 < t1) {
-        i32x4 ka[4][KS], kb_[4][KS];
+        kfrag_t ka[4][KS], kb_[4][KS];
         vstage_t vr;
         tile_t ga = kv.locate(t0, kv.fetch(t0)), gb;
         int pn = kv.fetch(min(t0 + 1, t1 - 1));  // page id of the NEXT look-ahead tile, on its way one step early
@@ -172,7 +177,7 @@
     } else {
       int pn = t0 < t1 ? kv.fetch(t0) : 0;
       for (int t = t0; t < t1; ++t) {
-        i32x4 ka[4][KS];
+        kfrag_t ka[4][KS];
         vstage_t vr;
         const tile_t ga = kv.locate(t, pn);
         pn = kv.fetch(min(t + 1, t1 - 1));

@@ -47,30 +47,44 @@ __device__ __forceinline__ int wave_min_i32(int v) {
 // family is measured against.  Included, they are the code they were, byte for byte.  The body includes attn_cache_tile.inc, the
 // text it shares with the decode body: a V tile belongs to the 256 threads here (NT, tix), the Q scale is the block's, and a tile
 // below every row limit of the wave calls compute without the key-limit compare.
-// The format is known to load_v and store_v only.
+// The V format is known to load_v and store_v only; KB = bits of a cached K code, known to load_k and the score product only.
 template <class KV, int DT, int D>
 __global__ __launch_bounds__(256) void attn_prefill_kernel(typename PrefillOf<KV>::type p) {
-  constexpr int VB = 16;
+  constexpr int VB = 16, KB = 8;
 #include "attn_prefill_body.inc"
 }
 // the same kernel over the fp8 V cache; the name keeps its family apart from the fp16 one in the code object
 template <class KV, int DT, int D>
 __global__ __launch_bounds__(256) void attn_prefill_v8_kernel(V8Params<typename PrefillOf<KV>::type, const float*> p) {
-  constexpr int VB = 8;
+  constexpr int VB = 8, KB = 8;
+#include "attn_prefill_body.inc"
+}
+// the same two kernels over the nibble-packed K cache (K4Params, lbfa_common.h): half the K bytes per key, widened in registers
+template <class KV, int DT, int D>
+__global__ __launch_bounds__(256) void attn_prefill_k4_kernel(K4Params<typename PrefillOf<KV>::type> p) {
+  constexpr int VB = 16, KB = 4;
+#include "attn_prefill_body.inc"
+}
+template <class KV, int DT, int D>
+__global__ __launch_bounds__(256) void attn_prefill_k4_v8_kernel(K4Params<V8Params<typename PrefillOf<KV>::type, const float*>> p) {
+  constexpr int VB = 8, KB = 4;
 #include "attn_prefill_body.inc"
 }
 
 // ---- host-side launchers (called from lbfa_api.hip) ----------------------------------------------------------------------
-// One launcher for the four cached prefills: the KV policy and the V format are the block's (CacheBlock, lbfa_common.h).
+// One launcher for the eight cached prefills: the KV policy and the formats of K and V are the block's (CacheBlock,
+// lbfa_common.h).  The file is compiled twice: as it is for the byte-per-code blocks, with LBFA_K4_UNIT for the packed-K ones.
 template <class P>
 hipError_t launch_prefill(const P& p, int dtype, int D, hipStream_t stream) {
   static_assert(CacheBlock<P>::op == CacheOp::kPrefill, "not a parameter block of the prefill kernels");
   using KV = std::conditional_t<CacheBlock<P>::paged, PagedKV, ContiguousKV>;
-  constexpr int VB = CacheBlock<P>::v_bits;
+  constexpr int VB = CacheBlock<P>::v_bits, KB = CacheBlock<P>::k_bits;
   dim3 grid((unsigned)p.nQ * (unsigned)p.splits, p.Hq, p.B);
 #define LBFA_PRE(DT, DD)                                                                                        \
   do {                                                                                                          \
-    if constexpr (VB == 8) hipLaunchKernelGGL((attn_prefill_v8_kernel<KV, DT, DD>), grid, dim3(256), 0, stream, p); \
+    if constexpr (KB == 4 && VB == 8) hipLaunchKernelGGL((attn_prefill_k4_v8_kernel<KV, DT, DD>), grid, dim3(256), 0, stream, p); \
+    else if constexpr (KB == 4) hipLaunchKernelGGL((attn_prefill_k4_kernel<KV, DT, DD>), grid, dim3(256), 0, stream, p); \
+    else if constexpr (VB == 8) hipLaunchKernelGGL((attn_prefill_v8_kernel<KV, DT, DD>), grid, dim3(256), 0, stream, p); \
     else hipLaunchKernelGGL((attn_prefill_kernel<KV, DT, DD>), grid, dim3(256), 0, stream, p);                  \
   } while (0)
   if (dtype == LBFA_F16) { if (D == 64) LBFA_PRE(LBFA_F16, 64); else LBFA_PRE(LBFA_F16, 128); }
@@ -80,9 +94,16 @@ hipError_t launch_prefill(const P& p, int dtype, int D, hipStream_t stream) {
   if (e != hipSuccess || p.splits == 1) return e;
   return launch_attn_decode_combine(p, dtype, D, stream);  // the partials are the decode kernel's: its second launch, unchanged
 }
+#ifndef LBFA_K4_UNIT
 template hipError_t launch_prefill(const PrefillParams&, int, int, hipStream_t);
 template hipError_t launch_prefill(const PagedPrefillParams&, int, int, hipStream_t);
 template hipError_t launch_prefill(const V8Params<PrefillParams, const float*>&, int, int, hipStream_t);
 template hipError_t launch_prefill(const V8Params<PagedPrefillParams, const float*>&, int, int, hipStream_t);
+#else
+template hipError_t launch_prefill(const K4Params<PrefillParams>&, int, int, hipStream_t);
+template hipError_t launch_prefill(const K4Params<PagedPrefillParams>&, int, int, hipStream_t);
+template hipError_t launch_prefill(const K4Params<V8Params<PrefillParams, const float*>>&, int, int, hipStream_t);
+template hipError_t launch_prefill(const K4Params<V8Params<PagedPrefillParams, const float*>>&, int, int, hipStream_t);
+#endif
 
 }  // namespace lbfa

@@ -1,11 +1,13 @@
 // Body of attn_prefill_kernel / attn_prefill_v8_kernel (attn_prefill.hip), included as text inside each with the kernel's template parameters, its parameter
-// block `p` and `constexpr int VB` (bits of a cached V element: 16 or 8) in scope.  See attn_prefill.hip.
+// block `p`, `constexpr int VB` (bits of a cached V element: 16 or 8) and `constexpr int KB` (bits of a cached K code: 8, or 4 for the
+// nibble-packed cache) in scope.  See attn_prefill.hip.
   constexpr int MB = 2;             // 16-row blocks per wave
   constexpr int KS = D / 64;        // k-steps of the score product
   constexpr int CB = D / 16;        // 16-channel blocks of O^T
   constexpr int VROW = 2 * D + 32;  // bytes per LDS row
   constexpr int VCH = D * VB / 512;  // 16-byte chunks of a V tile per thread
   typedef VStage<VCH, VB == 8 ? VCH : 0> vstage_t;  // fp8 V: and the scale of each chunk's key
+  typedef std::conditional_t<KB == 4, u32x2, i32x4> kfrag_t;  // a lane's 16 codes of one key as they are loaded
   typedef typename KV::tile_t tile_t;
   __shared__ __attribute__((aligned(16))) unsigned char smem[64 * VROW];
   __shared__ float wamax[4];
@@ -72,7 +74,10 @@
 #pragma unroll
     for (int rb = 0; rb < MB; ++rb)
 #pragma unroll
-      for (int s = 0; s < KS; ++s) qf[rb][s] = quant_codes16<false>(xq[rb][s], qsc, 0.f);  // the plain division
+      for (int s = 0; s < KS; ++s) {
+        qf[rb][s] = quant_codes16<false>(xq[rb][s], qsc, 0.f);  // the plain division
+        if constexpr (KB == 4) qf[rb][s] = k4_q_order(qf[rb][s]);
+      }
   }
   // the compare against the row limits is needed only in tiles that reach past the smallest limit of this wave's rows
   const int lim_min = wave_min_i32(min(lim[0], lim[1]));
@@ -83,7 +88,7 @@
   auto q_scale = [&](int) __attribute__((always_inline)) { return qsc; };  // one block of 128 rows: the workgroup's
 #include "attn_cache_tile.inc"
   // wave-uniform: a tile wholly below every limit of the wave's rows takes the form without the compare (same bits)
-  auto tile = [&](int t, tile_t gt, const i32x4 (&kf)[4][KS]) __attribute__((always_inline)) {
+  auto tile = [&](int t, tile_t gt, const kfrag_t (&kf)[4][KS]) __attribute__((always_inline)) {
     if (t * 64 + 64 <= lim_min) compute(t, gt, kf, std::false_type{});
     else compute(t, gt, kf, std::true_type{});
   };
@@ -93,7 +98,7 @@
   // page id of the tile after the look-ahead tile is fetched one step early (ContiguousKV: fetch() is nothing, locate(t) = t).
   // All four waves take every barrier: t0, t1 depend on the workgroup only.
   if (t0 < t1) {
-    i32x4 ka[4][KS], kb_[4][KS];
+    kfrag_t ka[4][KS], kb_[4][KS];
     vstage_t vr;
     tile_t ga = kv.locate(t0, kv.fetch(t0)), gb;
     int pn = kv.fetch(min(t0 + 1, t1 - 1));

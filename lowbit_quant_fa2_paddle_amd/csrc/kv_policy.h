@@ -124,4 +124,22 @@ __device__ __forceinline__ void store_vhat_chunk(unsigned char* image, int cidx,
   *reinterpret_cast<uint4*>(image + r * VROW + ch * 32 + 16) = in ? hi : make_uint4(0, 0, 0, 0);
 }
 
+
+// ---- the nibble-packed K cache (K4Params, lbfa_common.h): what a reader does with the packed words -----------------------------
+// The 8 bytes a lane fetches for one key hold its 16 channels c .. c + 15 as two words; the low nibbles of word 0 are channels
+// c + {0, 2, 4, 6}, its high nibbles c + {1, 3, 5, 7}, word 1 the same 8 channels on.  k4_widen turns them into the int8 operand of
+// the score MFMA in THAT channel order - {even of word 0, odd of word 0, even of word 1, odd of word 1} - as 16 * code: a nibble in
+// the top half of a byte IS 16 * code as int8 (|16 * code| <= 112), one shift and two masks per word and no sign extension.  An
+// integer dot product does not care in which order its channels are added, so Q's 16 codes per lane are put into the same order
+// once (k4_q_order), and the int32 score, 16 * (q . k) exactly, is shifted right by 4: the bits of the byte cache's score.
+__device__ __forceinline__ i32x4 k4_widen(u32x2 w) {
+  return i32x4{(int)((w.x << 4) & 0xF0F0F0F0u), (int)(w.x & 0xF0F0F0F0u), (int)((w.y << 4) & 0xF0F0F0F0u), (int)(w.y & 0xF0F0F0F0u)};
+}
+__device__ __forceinline__ i32x4 k4_q_order(i32x4 q) {
+  return i32x4{(int)__builtin_amdgcn_perm((unsigned)q[1], (unsigned)q[0], 0x06040200u),
+               (int)__builtin_amdgcn_perm((unsigned)q[1], (unsigned)q[0], 0x07050301u),
+               (int)__builtin_amdgcn_perm((unsigned)q[3], (unsigned)q[2], 0x06040200u),
+               (int)__builtin_amdgcn_perm((unsigned)q[3], (unsigned)q[2], 0x07050301u)};
+}
+
 }  // namespace lbfa

@@ -88,18 +88,32 @@ __device__ __forceinline__ uint2 quant_v_row_e4m3(const u32x4& raw, float& scale
 // (e4m3 codes with a scale per key, kv_policy.h).  Text, not a function the two kernels call: routed through an inlined function
 // the fp16 instances compile to other code than they had (same instructions, another schedule), and they are the yardstick the fp8
 // family is measured against.  Included, they are the code they were, byte for byte.
-// K is handled the same way in both.
+// K is quantised the same way in all of them; KB = bits of a stored K code: 8, or 4 for the nibble-packed cache (K4Params,
+// lbfa_common.h), which differs in the store alone - a thread's 8 codes become 4 bytes of its own, no lane exchange.
 template <class Dst, int DT, int D>
 __global__ __launch_bounds__(256) void kvcache_append_kernel(typename Dst::Params p) {
-  constexpr int VB = 16;
+  constexpr int VB = 16, KB = 8;
 #include "kvcache_append_body.inc"
 }
 // the same kernel for the fp8 V cache; the name keeps its family apart from the fp16 one in the code object
 template <class Dst, int DT, int D>
 __global__ __launch_bounds__(256) void kvcache_append_v8_kernel(V8Params<typename Dst::Params, float*> p) {
-  constexpr int VB = 8;
+  constexpr int VB = 8, KB = 8;
 #include "kvcache_append_body.inc"
 }
+// the same two kernels for the nibble-packed K cache
+template <class Dst, int DT, int D>
+__global__ __launch_bounds__(256) void kvcache_append_k4_kernel(K4Params<typename Dst::Params> p) {
+  constexpr int VB = 16, KB = 4;
+#include "kvcache_append_body.inc"
+}
+template <class Dst, int DT, int D>
+__global__ __launch_bounds__(256) void kvcache_append_k4_v8_kernel(K4Params<V8Params<typename Dst::Params, float*>> p) {
+  constexpr int VB = 8, KB = 4;
+#include "kvcache_append_body.inc"
+}
+
+#ifndef LBFA_K4_UNIT  // the mean kernel lives in the unit of the byte-per-code instances
 
 // Smooth-K mean of a first append whose sequences have different lengths: km[b, h, :] = storage dtype of the fp32 of the float64
 // mean over the new_lens[b] valid rows (zeros for an empty sequence).  One workgroup per (batch, head), fp64 sums in one fixed
@@ -133,6 +147,8 @@ __global__ __launch_bounds__(256) void kvcache_mean_kernel(RaggedMeanParams p) {
   }
 }
 
+#endif  // LBFA_K4_UNIT
+
 // ---- host-side launchers (called from lbfa_api.hip) ---------------------------------------------------------------
 static int kvcache_append_grid_x(int T) {
   // T rows starting anywhere in a block touch at most (T + 126) / 64 blocks; workgroup 0 takes the first and the last
@@ -140,16 +156,19 @@ static int kvcache_append_grid_x(int T) {
   return touched > 2 ? touched - 1 : 1;
 }
 
-// One launcher for the four appends: the destination policy and the V format are the block's (CacheBlock, lbfa_common.h).
+// One launcher for the eight appends: the destination policy and the formats of K and V are the block's (CacheBlock,
+// lbfa_common.h).  The file is compiled twice: as it is for the byte-per-code blocks, with LBFA_K4_UNIT for the packed-K ones.
 template <class P>
 hipError_t launch_append(const P& p, int dtype, int D, hipStream_t stream) {
   static_assert(CacheBlock<P>::op == CacheOp::kAppend, "not a parameter block of the append kernels");
   using Dst = std::conditional_t<CacheBlock<P>::paged, PagedDst, ContiguousDst>;
-  constexpr int VB = CacheBlock<P>::v_bits;
+  constexpr int VB = CacheBlock<P>::v_bits, KB = CacheBlock<P>::k_bits;
   dim3 grid(kvcache_append_grid_x(p.T), p.Hkv, p.B);
 #define LBFA_APP(DT, DD)                                                                                         \
   do {                                                                                                           \
-    if constexpr (VB == 8) hipLaunchKernelGGL((kvcache_append_v8_kernel<Dst, DT, DD>), grid, dim3(256), 0, stream, p); \
+    if constexpr (KB == 4 && VB == 8) hipLaunchKernelGGL((kvcache_append_k4_v8_kernel<Dst, DT, DD>), grid, dim3(256), 0, stream, p); \
+    else if constexpr (KB == 4) hipLaunchKernelGGL((kvcache_append_k4_kernel<Dst, DT, DD>), grid, dim3(256), 0, stream, p); \
+    else if constexpr (VB == 8) hipLaunchKernelGGL((kvcache_append_v8_kernel<Dst, DT, DD>), grid, dim3(256), 0, stream, p); \
     else hipLaunchKernelGGL((kvcache_append_kernel<Dst, DT, DD>), grid, dim3(256), 0, stream, p);                \
   } while (0)
   if (dtype == LBFA_F16) { if (D == 64) LBFA_APP(LBFA_F16, 64); else LBFA_APP(LBFA_F16, 128); }
@@ -157,11 +176,19 @@ hipError_t launch_append(const P& p, int dtype, int D, hipStream_t stream) {
 #undef LBFA_APP
   return hipGetLastError();
 }
+#ifndef LBFA_K4_UNIT
 template hipError_t launch_append(const AppendParams&, int, int, hipStream_t);
 template hipError_t launch_append(const PagedAppendParams&, int, int, hipStream_t);
 template hipError_t launch_append(const V8Params<AppendParams, float*>&, int, int, hipStream_t);
 template hipError_t launch_append(const V8Params<PagedAppendParams, float*>&, int, int, hipStream_t);
+#else
+template hipError_t launch_append(const K4Params<AppendParams>&, int, int, hipStream_t);
+template hipError_t launch_append(const K4Params<PagedAppendParams>&, int, int, hipStream_t);
+template hipError_t launch_append(const K4Params<V8Params<AppendParams, float*>>&, int, int, hipStream_t);
+template hipError_t launch_append(const K4Params<V8Params<PagedAppendParams, float*>>&, int, int, hipStream_t);
+#endif
 
+#ifndef LBFA_K4_UNIT
 hipError_t launch_kvcache_mean(const RaggedMeanParams& p, int dtype, int B, int D, hipStream_t stream) {
   dim3 grid(p.Hkv, B);
 #define LBFA_KM(DT, DD) hipLaunchKernelGGL((kvcache_mean_kernel<DT, DD>), grid, dim3(256), 0, stream, p)
@@ -170,5 +197,6 @@ hipError_t launch_kvcache_mean(const RaggedMeanParams& p, int dtype, int B, int 
 #undef LBFA_KM
   return hipGetLastError();
 }
+#endif
 
 }  // namespace lbfa

@@ -1,5 +1,6 @@
 // Body of kvcache_append_kernel / kvcache_append_v8_kernel (kvcache.hip), included as text inside each with the kernel's template parameters, its parameter
-// block `p` and `constexpr int VB` (bits of a cached V element: 16 or 8) in scope.  See kvcache.hip.
+// block `p`, `constexpr int VB` (bits of a cached V element: 16 or 8) and `constexpr int KB` (bits of a stored K code: 8, or 4 for the
+// nibble-packed cache) in scope.  See kvcache.hip.
   constexpr int CPR = D / 8;       // 16-byte chunks per row
   constexpr int RPP = 256 / CPR;   // rows per pass
   constexpr int NP = 64 / RPP;     // passes per 64-key block
@@ -80,7 +81,15 @@
       int q[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) q[i] = quant_code<false>(xs[ps][i], scale, 0.f);  // the plain division
-      if (row < end) *reinterpret_cast<uint2*>(codes + (int64_t)(row - r0) * D) = pack8_i8(q);
+      if constexpr (KB == 4) {
+        // packed: the row is D / 2 bytes and this thread's 8 codes (|q| <= 7) are 4 of them, channel 2 j low, 2 j + 1 high
+        unsigned w = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w |= (unsigned)((q[2 * j] & 15) | ((q[2 * j + 1] & 15) << 4)) << (8 * j);
+        if (row < end) *reinterpret_cast<unsigned*>(reinterpret_cast<uint8_t*>(p.k_codes) + (gb * 64 + (row - r0)) * (D / 2) + c * 4) = w;
+      } else {
+        if (row < end) *reinterpret_cast<uint2*>(codes + (int64_t)(row - r0) * D) = pack8_i8(q);
+      }
       if (row >= s0 && row < end) {
         if (open) *reinterpret_cast<uint4*>(tail + (int64_t)(row - r0) * D) = raw[ps];
         if constexpr (VB == 16) {

@@ -919,11 +919,12 @@ int lbfa_backward_varlen(const void* q, const void* k, const void* v, const void
 
 // ---------------------------------------------------------------------------------------------------------------
 // int8 KV cache and split-KV decode attention (kvcache.hip, attn_decode.hip, attn_prefill.hip), over a contiguous cache
-// [B, Hkv, capacity, D] or a pool of pages behind a block table, V as fp16 or as e4m3 codes with a scale per key.
+// [B, Hkv, capacity, D] or a pool of pages behind a block table, V as fp16 or as e4m3 codes with a scale per key, the K codes a
+// byte each or - the _k4 entry points - two to a byte.
 // An append and a cache read (decode or cached prefill) are described once each, AppendCall and ReadCall: one set of checks in one
 // order, one fill of the parameter block, one launch.  An entry point is ONE statement: it names itself and its parameter block
 // and passes its arguments in the order of its signature - the pool arguments as paged(...), v_scale beside v_cache, q_lens beside
-// seqlens.  The block is the whole choice: what the call is (paged, fp8 V, prefill), which fields are filled and which kernel
+// seqlens.  The block is the whole choice: what the call is (paged, fp8 V, packed K, prefill), which fields are filled and which kernel
 // runs all follow from its type (lbfa::CacheBlock), so the three cannot disagree.
 // ---------------------------------------------------------------------------------------------------------------
 }  // extern "C": the templates and overloads of this section need C++ linkage
@@ -991,7 +992,7 @@ struct AppendCall {
   int B, Hkv, T, D;
   Pool pool;
   int k_qmax;
-  bool paged, v8;  // what the parameter block is
+  bool paged, v8, k4;  // what the parameter block is
 };
 int check_append(AppendCall& c) {
   const char* who = c.who;
@@ -1003,6 +1004,7 @@ int check_append(AppendCall& c) {
   if (int st = check_pool(who, c.B, c.paged, c.pool)) return st;
   if (int st = check_dtype(c.dtype)) return st;
   if (int st = check_qmax(who, "k_qmax", c.k_qmax)) return st;
+  if (c.k4 && c.k_qmax != 7) return fail(LBFA_EINVAL, "%s: k_qmax must be 7 (the codes of a nibble-packed cache take 4 bits), got %d", who, c.k_qmax);
   if (int st = check_input16(who, "k_new", c.k_new)) return st;
   if (int st = check_input16(who, "v_new", c.v_new)) return st;
   if (!aligned(c.k_codes, 16) || !aligned(c.v.p, 16) || !aligned(c.k_tail, 16) || !aligned(c.km, 16) || !aligned(c.k_scale, 4) ||
@@ -1138,7 +1140,7 @@ int run_append(const char* who, const void* k_new, const void* v_new, int dtype,
   using Is = lbfa::CacheBlock<P>;
   static_assert(Is::op == lbfa::CacheOp::kAppend, "run_append takes the parameter block of an append");
   AppendCall c{who, dense(k_new, strides_k), dense(v_new, strides_v), dtype, new_lens, km, k_codes, k_scale, v, k_tail, seqlens,
-               B, Hkv, T, D, pool, k_qmax, Is::paged, Is::v_bits == 8};
+               B, Hkv, T, D, pool, k_qmax, Is::paged, Is::v_bits == 8, Is::k_bits == 4};
   if (int st = check_append(c)) return st;
   const P p = block_of<P>(c);
   g_err[0] = 0;
@@ -1165,6 +1167,10 @@ int run_read(const char* who, const void* q, int dtype, const int8_t* k_codes, c
 // the parameter blocks of the fp8 V cache
 template <class Base> using AppendV8 = lbfa::V8Params<Base, float*>;
 template <class Base> using ReadV8 = lbfa::V8Params<Base, const float*>;
+// the parameter blocks of the nibble-packed K cache: the sibling's block, k_codes two codes per byte behind the same pointer
+template <class Base> using K4 = lbfa::K4Params<Base>;
+int8_t* nibbles(uint8_t* k_codes) { return reinterpret_cast<int8_t*>(k_codes); }
+const int8_t* nibbles(const uint8_t* k_codes) { return reinterpret_cast<const int8_t*>(k_codes); }
 }  // namespace
 
 extern "C" {
@@ -1350,6 +1356,134 @@ int lbfa_prefill_paged_v8(const void* q, int dtype, const int8_t* k_codes, const
                           int max_pages_per_seq, int max_seqlen_k, int num_splits, const int64_t strides_q[3],
                           const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream) {
   return run_read<ReadV8<lbfa::PagedPrefillParams>>("lbfa_prefill_paged_v8", q, dtype, k_codes, k_scale, {v_cache, v_scale}, km,
+                                                    {seqlens, q_lens}, o, lse, workspace, workspace_bytes, B, Hq, Hkv, Sq, D,
+                                                    paged(block_table, slots, num_slots, num_pages, page_size, max_pages_per_seq),
+                                                    max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax, is_causal,
+                                                    stream);
+}
+
+// The nibble-packed K cache: every entry point above once more with k_codes as two codes per byte (uint8 [.., key, D / 2]: byte j
+// of a row holds channel 2 j in bits 0..3 and channel 2 j + 1 in bits 4..7).  Each is its sibling's statement over K4<block> with
+// k_codes passed as the bytes they are; an append takes k_qmax 7 only.
+int lbfa_kvcache_append_k4(const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
+                           uint8_t* k_codes, float* k_scale, void* v_cache, void* k_tail, const int32_t* seqlens,
+                           int B, int Hkv, int T, int D, int capacity, const int64_t strides_k[3], const int64_t strides_v[3],
+                           int k_qmax, void* stream) {
+  return run_append<K4<lbfa::AppendParams>>("lbfa_kvcache_append_k4", k_new, v_new, dtype, new_lens, km, nibbles(k_codes), k_scale, {v_cache}, k_tail,
+                                        seqlens, B, Hkv, T, D, contiguous(capacity), strides_k, strides_v, k_qmax, stream);
+}
+
+int lbfa_kvcache_paged_append_k4(const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
+                                 uint8_t* k_codes, float* k_scale, void* v_cache, void* k_tail, const int32_t* seqlens,
+                                 const int32_t* block_table, const int32_t* slots, int B, int Hkv, int T, int D, int num_slots,
+                                 int num_pages, int page_size, int max_pages_per_seq, const int64_t strides_k[3],
+                                 const int64_t strides_v[3], int k_qmax, void* stream) {
+  return run_append<K4<lbfa::PagedAppendParams>>("lbfa_kvcache_paged_append_k4", k_new, v_new, dtype, new_lens, km, nibbles(k_codes), k_scale, {v_cache},
+                                             k_tail, seqlens, B, Hkv, T, D,
+                                             paged(block_table, slots, num_slots, num_pages, page_size, max_pages_per_seq), strides_k,
+                                             strides_v, k_qmax, stream);
+}
+
+int lbfa_kvcache_append_k4_v8(const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
+                              uint8_t* k_codes, float* k_scale, uint8_t* v_cache, float* v_scale, void* k_tail, const int32_t* seqlens,
+                              int B, int Hkv, int T, int D, int capacity, const int64_t strides_k[3], const int64_t strides_v[3],
+                              int k_qmax, void* stream) {
+  return run_append<K4<AppendV8<lbfa::AppendParams>>>("lbfa_kvcache_append_k4_v8", k_new, v_new, dtype, new_lens, km, nibbles(k_codes), k_scale,
+                                                  {v_cache, v_scale}, k_tail, seqlens, B, Hkv, T, D, contiguous(capacity), strides_k,
+                                                  strides_v, k_qmax, stream);
+}
+
+int lbfa_kvcache_paged_append_k4_v8(const void* k_new, const void* v_new, int dtype, const int32_t* new_lens, const void* km,
+                                    uint8_t* k_codes, float* k_scale, uint8_t* v_cache, float* v_scale, void* k_tail,
+                                    const int32_t* seqlens, const int32_t* block_table, const int32_t* slots, int B, int Hkv, int T,
+                                    int D, int num_slots, int num_pages, int page_size, int max_pages_per_seq,
+                                    const int64_t strides_k[3], const int64_t strides_v[3], int k_qmax, void* stream) {
+  return run_append<K4<AppendV8<lbfa::PagedAppendParams>>>("lbfa_kvcache_paged_append_k4_v8", k_new, v_new, dtype, new_lens, km, nibbles(k_codes),
+                                                       k_scale, {v_cache, v_scale}, k_tail, seqlens, B, Hkv, T, D,
+                                                       paged(block_table, slots, num_slots, num_pages, page_size, max_pages_per_seq),
+                                                       strides_k, strides_v, k_qmax, stream);
+}
+
+int lbfa_decode_k4(const void* q, int dtype, const uint8_t* k_codes, const float* k_scale, const void* v_cache, const void* km,
+                   const int32_t* seqlens, void* o, float* lse, void* workspace, size_t workspace_bytes,
+                   int B, int Hq, int Hkv, int Sq, int D, int capacity, int max_seqlen_k, int num_splits,
+                   const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream) {
+  return run_read<K4<lbfa::DecodeParams>>("lbfa_decode_k4", q, dtype, nibbles(k_codes), k_scale, {v_cache}, km, {seqlens}, o, lse, workspace,
+                                      workspace_bytes, B, Hq, Hkv, Sq, D, contiguous(capacity), max_seqlen_k, num_splits, strides_q,
+                                      strides_o, sm_scale, q_qmax, is_causal, stream);
+}
+
+int lbfa_decode_paged_k4(const void* q, int dtype, const uint8_t* k_codes, const float* k_scale, const void* v_cache, const void* km,
+                         const int32_t* seqlens, const int32_t* block_table, const int32_t* slots, void* o, float* lse,
+                         void* workspace, size_t workspace_bytes, int B, int Hq, int Hkv, int Sq, int D, int num_slots, int num_pages,
+                         int page_size, int max_pages_per_seq, int max_seqlen_k, int num_splits, const int64_t strides_q[3],
+                         const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream) {
+  return run_read<K4<lbfa::PagedDecodeParams>>("lbfa_decode_paged_k4", q, dtype, nibbles(k_codes), k_scale, {v_cache}, km, {seqlens}, o, lse,
+                                           workspace, workspace_bytes, B, Hq, Hkv, Sq, D,
+                                           paged(block_table, slots, num_slots, num_pages, page_size, max_pages_per_seq),
+                                           max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax, is_causal, stream);
+}
+
+int lbfa_decode_k4_v8(const void* q, int dtype, const uint8_t* k_codes, const float* k_scale, const uint8_t* v_cache, const float* v_scale,
+                      const void* km, const int32_t* seqlens, void* o, float* lse, void* workspace, size_t workspace_bytes,
+                      int B, int Hq, int Hkv, int Sq, int D, int capacity, int max_seqlen_k, int num_splits,
+                      const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream) {
+  return run_read<K4<ReadV8<lbfa::DecodeParams>>>("lbfa_decode_k4_v8", q, dtype, nibbles(k_codes), k_scale, {v_cache, v_scale}, km, {seqlens}, o,
+                                              lse, workspace, workspace_bytes, B, Hq, Hkv, Sq, D, contiguous(capacity),
+                                              max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax, is_causal, stream);
+}
+
+int lbfa_decode_paged_k4_v8(const void* q, int dtype, const uint8_t* k_codes, const float* k_scale, const uint8_t* v_cache,
+                            const float* v_scale, const void* km, const int32_t* seqlens, const int32_t* block_table,
+                            const int32_t* slots, void* o, float* lse, void* workspace, size_t workspace_bytes, int B, int Hq, int Hkv,
+                            int Sq, int D, int num_slots, int num_pages, int page_size, int max_pages_per_seq, int max_seqlen_k,
+                            int num_splits, const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax,
+                            int is_causal, void* stream) {
+  return run_read<K4<ReadV8<lbfa::PagedDecodeParams>>>("lbfa_decode_paged_k4_v8", q, dtype, nibbles(k_codes), k_scale, {v_cache, v_scale}, km,
+                                                   {seqlens}, o, lse, workspace, workspace_bytes, B, Hq, Hkv, Sq, D,
+                                                   paged(block_table, slots, num_slots, num_pages, page_size, max_pages_per_seq),
+                                                   max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax, is_causal,
+                                                   stream);
+}
+
+int lbfa_prefill_k4(const void* q, int dtype, const uint8_t* k_codes, const float* k_scale, const void* v_cache, const void* km,
+                    const int32_t* seqlens, const int32_t* q_lens, void* o, float* lse, void* workspace, size_t workspace_bytes,
+                    int B, int Hq, int Hkv, int Sq, int D, int capacity, int max_seqlen_k, int num_splits,
+                    const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream) {
+  return run_read<K4<lbfa::PrefillParams>>("lbfa_prefill_k4", q, dtype, nibbles(k_codes), k_scale, {v_cache}, km, {seqlens, q_lens}, o, lse,
+                                       workspace, workspace_bytes, B, Hq, Hkv, Sq, D, contiguous(capacity), max_seqlen_k,
+                                       num_splits, strides_q, strides_o, sm_scale, q_qmax, is_causal, stream);
+}
+
+int lbfa_prefill_paged_k4(const void* q, int dtype, const uint8_t* k_codes, const float* k_scale, const void* v_cache, const void* km,
+                          const int32_t* seqlens, const int32_t* q_lens, const int32_t* block_table, const int32_t* slots, void* o,
+                          float* lse, void* workspace, size_t workspace_bytes, int B, int Hq, int Hkv, int Sq, int D, int num_slots,
+                          int num_pages, int page_size, int max_pages_per_seq, int max_seqlen_k, int num_splits,
+                          const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal,
+                          void* stream) {
+  return run_read<K4<lbfa::PagedPrefillParams>>("lbfa_prefill_paged_k4", q, dtype, nibbles(k_codes), k_scale, {v_cache}, km, {seqlens, q_lens}, o,
+                                            lse, workspace, workspace_bytes, B, Hq, Hkv, Sq, D,
+                                            paged(block_table, slots, num_slots, num_pages, page_size, max_pages_per_seq),
+                                            max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax, is_causal, stream);
+}
+
+int lbfa_prefill_k4_v8(const void* q, int dtype, const uint8_t* k_codes, const float* k_scale, const uint8_t* v_cache, const float* v_scale,
+                       const void* km, const int32_t* seqlens, const int32_t* q_lens, void* o, float* lse, void* workspace,
+                       size_t workspace_bytes, int B, int Hq, int Hkv, int Sq, int D, int capacity, int max_seqlen_k, int num_splits,
+                       const int64_t strides_q[3], const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream) {
+  return run_read<K4<ReadV8<lbfa::PrefillParams>>>("lbfa_prefill_k4_v8", q, dtype, nibbles(k_codes), k_scale, {v_cache, v_scale}, km,
+                                               {seqlens, q_lens}, o, lse, workspace, workspace_bytes, B, Hq, Hkv, Sq, D,
+                                               contiguous(capacity), max_seqlen_k, num_splits, strides_q, strides_o, sm_scale,
+                                               q_qmax, is_causal, stream);
+}
+
+int lbfa_prefill_paged_k4_v8(const void* q, int dtype, const uint8_t* k_codes, const float* k_scale, const uint8_t* v_cache,
+                             const float* v_scale, const void* km, const int32_t* seqlens, const int32_t* q_lens,
+                             const int32_t* block_table, const int32_t* slots, void* o, float* lse, void* workspace,
+                             size_t workspace_bytes, int B, int Hq, int Hkv, int Sq, int D, int num_slots, int num_pages, int page_size,
+                             int max_pages_per_seq, int max_seqlen_k, int num_splits, const int64_t strides_q[3],
+                             const int64_t strides_o[3], double sm_scale, int q_qmax, int is_causal, void* stream) {
+  return run_read<K4<ReadV8<lbfa::PagedPrefillParams>>>("lbfa_prefill_paged_k4_v8", q, dtype, nibbles(k_codes), k_scale, {v_cache, v_scale}, km,
                                                     {seqlens, q_lens}, o, lse, workspace, workspace_bytes, B, Hq, Hkv, Sq, D,
                                                     paged(block_table, slots, num_slots, num_pages, page_size, max_pages_per_seq),
                                                     max_seqlen_k, num_splits, strides_q, strides_o, sm_scale, q_qmax, is_causal,

@@ -332,8 +332,16 @@ struct V8Params : Base {
   ScalePtr v_scale;
 };
 
+// The nibble-packed K cache (k_packed): `k_codes` of the block points at two codes per byte, rows of D / 2 bytes in the layout of
+// the byte-per-code cache - byte j of a row holds channel 2 j in bits 0..3 and channel 2 j + 1 in bits 4..7, each the two's
+// complement 4-bit value of the code (qmax 7: never -8).  A 64-key tile is 32 D contiguous bytes.  Scales, tail, km and V are the
+// byte cache's.  The parameter block of a packed-K instance is its sibling's - fp16 or fp8 V - with nothing added: the type alone
+// selects the *_k4_kernel / *_k4_v8_kernel instances.
+template <class Base>
+struct K4Params : Base {};
+
 // What a parameter block of the cache kernels selects, written once: the family it belongs to, whether its keys lie in pages and
-// the bits of a cached V element.  The launchers pick the kernel instance from it and the C-ABI layer what to fill in.  Only the
+// the bits of a cached V element and of a cached K code.  The launchers pick the kernel instance from it and the C-ABI layer what to fill in.  Only the
 // blocks listed here have one: anything else - a base of one of them included - does not compile.
 enum class CacheOp { kAppend, kDecode, kPrefill };
 template <CacheOp OP, bool PAGED>
@@ -341,6 +349,7 @@ struct CacheBlockOf {
   static constexpr CacheOp op = OP;
   static constexpr bool paged = PAGED;
   static constexpr int v_bits = 16;
+  static constexpr int k_bits = 8;
 };
 template <class P> struct CacheBlock;
 template <> struct CacheBlock<AppendParams> : CacheBlockOf<CacheOp::kAppend, false> {};
@@ -353,9 +362,14 @@ template <class Base, class ScalePtr>
 struct CacheBlock<V8Params<Base, ScalePtr>> : CacheBlock<Base> {
   static constexpr int v_bits = 8;
 };
+template <class Base>
+struct CacheBlock<K4Params<Base>> : CacheBlock<Base> {
+  static constexpr int k_bits = 4;
+};
 
-// The launchers of the three families: one host template each, defined and explicitly instantiated for its four blocks (contiguous
-// or paged, fp16 or fp8 V) in kvcache.hip / attn_decode.hip / attn_prefill.hip.  P is deduced exactly, never converted to a base,
+// The launchers of the three families: one host template each, defined and explicitly instantiated for its eight blocks (contiguous
+// or paged, fp16 or fp8 V, byte or packed K) in kvcache.hip / attn_decode.hip / attn_prefill.hip; the packed-K instances are a
+// second compilation of the same file (LBFA_K4_UNIT), so that the two halves build side by side.  P is deduced exactly, never converted to a base,
 // and a block without an instantiation does not link.
 template <class P> hipError_t launch_append(const P& p, int dtype, int D, hipStream_t stream);
 template <class P> hipError_t launch_decode(const P& p, int dtype, int D, hipStream_t stream);

@@ -21,9 +21,18 @@ append bit for bit, and the K state is exactly that of a `v_bits=16` cache.  A r
 scale)` (`dequantized_v()`), with `|V^ - V| <= (2^-4 + 2^-10) |V| + 2^-10 scale + 2^-24` per element, and a read equals, bit for
 bit, the same read of a `v_bits=16` cache whose `v` holds V^.  `k_bits` and `v_bits` are independent.
 
-Not here: prefix sharing / copy-on-write between sequences, fp8 P or an fp8 MFMA over the cache (V^ enters the fp16 MFMA), nibble-
-packed int4 (the +-7 codes take a byte each), a backward through the cache, Paddle tensors, routing `lowbit_fa_decode` calls with
-more than 64 rows to the prefill kernel (decode keeps refusing them).
+`k_packed=True` (either cache, with `k_bits=4` only; the default False changes nothing) keeps the +-7 codes of `k_bits=4` two to a
+byte (`lbfa_*_k4`, `lbfa_*_k4_v8`): `k_codes` is uint8 [.., keys, Dp / 2], byte j of a row holds channel 2 j in bits 0..3 and
+channel 2 j + 1 in bits 4..7, each nibble the two's-complement 4-bit value of the code (never -8).  Without it `k_bits=4` costs
+accuracy and buys nothing: the codes take a byte each.  Packed, the decode kernel streams 2.5 D bytes per key instead of 3 D (with
+`v_bits=8`: 1.5 D + 4 instead of 2 D + 4) and the smallest cache takes about half the memory of the default one.  Scales, tail,
+`km`, V and the re-quantisation of the open block are the byte cache's; a row is packed from its own codes, so any append schedule
+still gives the one-shot state bit for bit, and a read equals, bit for bit, the same read of the byte-per-code `k_bits=4` cache
+(an integer score does not depend on the order of its channels).  `unpacked_k_codes()` gives the int8 codes back.
+
+Not here: prefix sharing / copy-on-write between sequences, fp8 P or an fp8 MFMA over the cache (V^ enters the fp16 MFMA), an
+int4 MFMA or a packed Q (the nibbles are widened to the int8 MFMA's operands in registers), a backward through the cache, Paddle
+tensors, routing `lowbit_fa_decode` calls with more than 64 rows to the prefill kernel (decode keeps refusing them).
 """
 from __future__ import annotations
 
@@ -89,13 +98,22 @@ def _first_append_mean(lib, ops, k, k3, new_lens, km, B: int, H: int, T: int, D:
                                          stream), lib)
 
 
+def _unpack_nibbles(packed):
+    """uint8 [.., n] of two's-complement nibble pairs (low: even channel) -> int8 [.., 2 n]"""
+    import torch
+    w = packed.to(torch.int16)
+    pair = torch.stack((w & 15, w >> 4), dim=-1)
+    return (pair - 16 * (pair >> 3)).to(torch.int8).reshape(*packed.shape[:-1], 2 * packed.shape[-1])
+
+
 class _CacheState:
     """What the two caches share: the checks of the formats, the state tensors behind a leading shape, and the argument list of
     an entry point."""
 
     v_bits = 16  # bits of a cached V element; 8 adds `v_scale`
+    k_packed = False  # True: `k_codes` holds two 4-bit codes per byte
 
-    def _check_formats(self, k_bits: int, v_bits: int, dtype):
+    def _check_formats(self, k_bits: int, v_bits: int, dtype, k_packed: bool = False):
         import torch
         if k_bits not in (8, 4):
             raise ValueError(f"k_bits must be 8 or 4, got {k_bits}")
@@ -103,6 +121,9 @@ class _CacheState:
             raise ValueError(f"v_bits must be 16 or 8, got {v_bits}")
         if dtype not in (torch.float16, torch.bfloat16):
             raise ValueError("dtype must be torch.float16 or torch.bfloat16")
+        if k_packed and k_bits != 4:
+            raise ValueError(f"k_packed=True needs k_bits=4 (the codes must fit a nibble), got k_bits={k_bits}")
+        self.k_packed = bool(k_packed)
         self.v_bits, self.k_qmax = int(v_bits), 127 if k_bits == 8 else 7
 
     def _allocate(self, num_kv_heads: int, head_dim: int, dtype, device, smooth_k: bool, blocks: int, keys: int, seqs: int):
@@ -119,7 +140,7 @@ class _CacheState:
 
         def zeros(shape, dt):
             return torch.zeros(shape, dtype=dt, device=self.device)
-        self.k_codes = zeros((blocks, H, keys, D), torch.int8)
+        self.k_codes = zeros((blocks, H, keys, D // 2), torch.uint8) if self.k_packed else zeros((blocks, H, keys, D), torch.int8)
         self.k_scale = zeros((blocks, H, keys // _lib.BLKK), torch.float32)
         self.v = zeros((blocks, H, keys, D), torch.uint8 if self.v_bits == 8 else torch.float16)
         if self.v_bits == 8:
@@ -138,8 +159,13 @@ class _CacheState:
             v = (v.view(torch.float8_e4m3fn).float() * self.v_scale[..., None]).to(torch.float16)
         return v[..., :self.head_dim]
 
+    def unpacked_k_codes(self):
+        """Debugging aid (torch ops, read-only): the K codes as int8 in the shape of the byte-per-code cache, [.., keys, Dp] -
+        `k_codes` itself unless `k_packed`.  Rows no sequence holds are meaningless."""
+        return _unpack_nibbles(self.k_codes) if self.k_packed else self.k_codes
+
     def _call(self, lib, name: str, head, mid, dims, tail, slot_t=None):
-        """Calls entry point `name` (+ "_v8" over an fp8 V cache) with the argument list of include/lowbit_fa.h, put together from
+        """Calls entry point `name` (+ "_k4" over a packed K cache, + "_v8" over an fp8 V cache) with the argument list of include/lowbit_fa.h, put together from
         its named pieces:  head (.. v_cache), [v_scale], mid (.. seqlens[, q_lens]), [block_table, slots], dims (.. D),
         capacity | num_slots .. max_pages_per_seq, tail (.. stream)"""
         v8 = self.v_bits == 8
@@ -148,7 +174,7 @@ class _CacheState:
             extent = (self.max_seqs, self.num_pages, self.page_size, self.max_pages_per_seq)
         else:
             table, extent = (), (self.capacity,)
-        entry = getattr(lib, name + ("_v8" if v8 else ""))
+        entry = getattr(lib, name + ("_k4" if self.k_packed else "") + ("_v8" if v8 else ""))
         _lib.check(entry(*head, *((self.v_scale.data_ptr(),) if v8 else ()), *mid, *table, *dims, *extent, *tail), lib)
 
     def _append_rows(self, lib, name: str, ops, k, v, new_lens, n: int, H: int, T: int, k3, v3, stream, slot_t=None):
@@ -167,12 +193,13 @@ class LowbitKVCache(_CacheState):
     k_tail [B, Hkv, 64, Dp] (raw rows of the open 64-key block), km [B, Hkv, Dp] or None, seqlens int32 [B]; Dp = head_dim
     zero-padded to 64 / 128.  `km`, the smooth-K mean, is taken from the FIRST append and fixed from then on.
     With `v_bits=8`, v is uint8 [B, Hkv, cap, Dp] (e4m3fn bit patterns) and v_scale fp32 [B, Hkv, cap] holds the scale of each row
-    (module docstring); with the default 16 there is no v_scale.
+    (module docstring); with the default 16 there is no v_scale.  With `k_packed=True` (needs `k_bits=4`), k_codes is uint8
+    [B, Hkv, cap, Dp / 2], two codes per byte (module docstring).
     No host read of `seqlens` happens anywhere: the host only tracks an upper bound of the lengths (the rows offered so far)."""
 
     def __init__(self, batch: int, num_kv_heads: int, head_dim: int, capacity: int, dtype, device, k_bits: int = 8,
-                 smooth_k: bool = True, v_bits: int = 16):
-        self._check_formats(k_bits, v_bits, dtype)
+                 smooth_k: bool = True, v_bits: int = 16, k_packed: bool = False):
+        self._check_formats(k_bits, v_bits, dtype, k_packed)
         if batch <= 0 or num_kv_heads <= 0 or capacity <= 0:
             raise ValueError("batch, num_kv_heads and capacity must be positive")
         self.batch = int(batch)
@@ -211,7 +238,7 @@ class LowbitKVCache(_CacheState):
     def dequantized_k(self):
         """Debugging aid (torch ops, read-only): fp32 [B, Hkv, capacity, head_dim] = codes * scale (+ km).  Rows at or past
         seqlens[b] are meaningless."""
-        k = self.k_codes.float() * self.k_scale.repeat_interleave(_lib.BLKK, dim=2)[..., None]
+        k = self.unpacked_k_codes().float() * self.k_scale.repeat_interleave(_lib.BLKK, dim=2)[..., None]
         if self.km is not None:
             k = k + self.km.float()[:, :, None, :]
         return k[..., :self.head_dim]
@@ -296,15 +323,17 @@ class LowbitPagedKVCache(_CacheState):
     [num_pages, Hkv, page_size, Dp], k_scale fp32 [num_pages, Hkv, page_size / 64], v fp16 [num_pages, Hkv, page_size, Dp],
     block_table int32 [max_seqs, max_pages_per_seq], k_tail [max_seqs, Hkv, 64, Dp], km [max_seqs, Hkv, Dp] or None, seqlens int32
     [max_seqs].  With `v_bits=8`, v is uint8 [num_pages, Hkv, page_size, Dp] (e4m3fn bit patterns) and v_scale fp32 [num_pages, Hkv,
-    page_size] holds the scale of each row, addressed by the same page and row as the codes.  `allocator` (a `PageAllocator`) is the host side.  `km` is PER SEQUENCE: a slot that holds nothing is fresh, and
+    page_size] holds the scale of each row, addressed by the same page and row as the codes.  With `k_packed=True` (needs
+    `k_bits=4`), k_codes is uint8 [num_pages, Hkv, page_size, Dp / 2], two codes per byte, a 64-key tile 32 Dp contiguous bytes
+    inside its page.  `allocator` (a `PageAllocator`) is the host side.  `km` is PER SEQUENCE: a slot that holds nothing is fresh, and
     takes its mean from its first append.  As in `LowbitKVCache` no host read of device lengths happens anywhere: pages are
     allocated for the upper bound of each length."""
 
     def __init__(self, num_pages: int, page_size: int, num_kv_heads: int, head_dim: int, max_seqs: int, max_pages_per_seq: int,
                  dtype, device, k_bits: int = 8, smooth_k: bool = True, page_order: Optional[Iterable[int]] = None,
-                 v_bits: int = 16):
+                 v_bits: int = 16, k_packed: bool = False):
         import torch
-        self._check_formats(k_bits, v_bits, dtype)
+        self._check_formats(k_bits, v_bits, dtype, k_packed)
         if num_kv_heads <= 0:
             raise ValueError("num_kv_heads must be positive")
         self.allocator = PageAllocator(num_pages, page_size, max_seqs, max_pages_per_seq, page_order)
@@ -374,12 +403,13 @@ class LowbitPagedKVCache(_CacheState):
     def gather(self, slot: int):
         """Debugging aid (torch ops, read-only): the sequence in `slot` through its block table as contiguous tensors - codes
         int8 [Hkv, n, Dp], scales fp32 [Hkv, n / 64], V fp16 [Hkv, n, Dp], n = its pages * page_size; with `v_bits=8` V is the
-        uint8 codes and a fourth tensor follows, their scales fp32 [Hkv, n].  Rows at or past seqlens[slot] are meaningless."""
+        uint8 codes and a fourth tensor follows, their scales fp32 [Hkv, n]; with `k_packed` the codes are the packed bytes, uint8
+        [Hkv, n, Dp / 2].  Rows at or past seqlens[slot] are meaningless."""
         import torch
         idx = torch.tensor(self.allocator.pages[slot], dtype=torch.int64, device=self.device)
         H, D = self.num_kv_heads, self.padded_head_dim
         # (contiguous() : with one 64-key block per page the reshape of the scales is a strided view)
-        out = (self.k_codes[idx].transpose(0, 1).reshape(H, -1, D).contiguous(),
+        out = (self.k_codes[idx].transpose(0, 1).reshape(H, -1, self.k_codes.shape[-1]).contiguous(),
                self.k_scale[idx].transpose(0, 1).reshape(H, -1).contiguous(),
                self.v[idx].transpose(0, 1).reshape(H, -1, D).contiguous())
         if self.v_bits == 8:

@@ -13,6 +13,9 @@ percentile per arm:
   prefill_v8     `lowbit_fa_prefill` on a `LowbitKVCache(..., v_bits=8)` holding the same keys (V as e4m3 codes with a scale per
                  key), the chosen num_splits.  Prefill is not bound by the stream: the arm only has to be no slower than `prefill` -
                  `prefill_v8_over_prefill` is the ratio of the medians, `prefill_v8_not_above_prefill_p90` the verdict
+  prefill_k4     `lowbit_fa_prefill` on a `LowbitKVCache(..., k_bits=4, k_packed=True)` holding the same keys (the +-7 K codes two
+                 to a byte), the chosen num_splits; measured like `prefill_v8`: `prefill_k4_over_prefill`,
+                 `prefill_k4_not_above_prefill_p90`, and `prefill_k4_vs_prefill_output`, the accuracy price of 4-bit K codes
   dense_int8     the dense int8 operator on the 16-bit K, V at the same Sq x Sk, NON-causal (its causal mask needs Sq == Sk) - all a
                  user could do before; it takes the mean, quantises and re-reads the whole context on every call
   dense_causal   the dense int8 operator, causal, where Sq == Sk
@@ -26,7 +29,7 @@ Every arm is CHECKED before it is timed (`oracle_check`): the numpy oracle is to
 at a reduced shape of the same kind - B 1, Hq 8 / Hkv 2 (the same G), the same D, mask and num_splits, Sq cut to 256 and the
 context to 1024 keys (Sq = n stays Sq = n) - and every element of its output is held to the operator bound
 |dO| <= 2e-3 + 2e-3 |O| (tests/kvcache_reference.py `o_bound`) of ITS oracle on those inputs: `oracle_prefill` on a numpy cache
-for the prefill arms (`prefill_v8`: on the numpy cache's codes and V^, tests/v8_reference.py), `oracle_decode` per 64-row piece for the decode loop, the dense oracle (`lowbit_fa_forward`) for the dense
+for the prefill arms (`prefill_v8`: on the numpy cache's codes and V^, tests/v8_reference.py; `prefill_k4`: on a numpy cache quantised with qmax 7), `oracle_decode` per 64-row piece for the decode loop, the dense oracle (`lowbit_fa_forward`) for the dense
 arms, fp32 attention for fp16 SDPA.  A ratio above 1 ends the run with an error; the ratios go into the JSON
 (`oracle_check`).  `max_abs_diff_vs_fp32_attention_last_rows` is a figure at the timed size, beside the check.
 Prints one JSON document (and writes it to --out).
@@ -95,7 +98,7 @@ def _reference_rows(q, k, v, rows, n, Sq, causal):
     return torch.einsum("bhgqk,bhkd->bhgqd", torch.softmax(s, dim=-1), v.float()).reshape(q.shape[0], HQ, -1, q.shape[-1])
 
 
-def make_arms(lb, q, k, v, cache, causal, splits, with_sdpa, cache8=None):
+def make_arms(lb, q, k, v, cache, causal, splits, with_sdpa, cache8=None, cache_k4=None):
     """name -> call, for inputs of any size: the timed arms and their reduced twins of `oracle_check` are built here alike"""
     Sq, n, dev = q.shape[2], k.shape[2], q.device
     arms = {
@@ -105,6 +108,8 @@ def make_arms(lb, q, k, v, cache, causal, splits, with_sdpa, cache8=None):
     }
     if cache8 is not None:
         arms["prefill_v8"] = lambda: lb.lowbit_fa_prefill(q, cache8, is_causal=causal, num_splits=splits)
+    if cache_k4 is not None:
+        arms["prefill_k4"] = lambda: lb.lowbit_fa_prefill(q, cache_k4, is_causal=causal, num_splits=splits)
     if causal and Sq == n:
         arms["dense_causal"] = lambda: lb.lowbit_fa_qk_int8_pv_fp16_triton(q, k, v, is_causal=True)
     if with_sdpa:
@@ -146,6 +151,9 @@ def _oracle_references(D, Sq, n, causal):
     want = {"prefill": pr.oracle_prefill(orc, q_i8, q_scale, ref16, [Sq], causal=causal, out_dtype="fp16")[0]}
     want["prefill_1"] = want["prefill"]
     want["prefill_v8"] = pr.oracle_prefill(orc, q_i8, q_scale, ref, [Sq], causal=causal, out_dtype="fp16")[0]
+    ref4 = kr.CacheRef(orc, 1, hkv, D, (n + 63) // 64 * 64, "fp16", qmax=7)  # what the packed cache holds, a byte per code
+    ref4.append(k, v)
+    want["prefill_k4"] = pr.oracle_prefill(orc, q_i8, q_scale, ref4, [Sq], causal=causal, out_dtype="fp16")[0]
     want["dense_int8"] = orc.lowbit_fa_forward(q, k, v, is_causal=False, tail="neg_inf", amax_floor=1e-7)
     if causal and Sq == n:
         want["dense_causal"] = orc.lowbit_fa_forward(q, k, v, is_causal=True, tail="neg_inf", amax_floor=1e-7)
@@ -176,9 +184,11 @@ def oracle_check(lb, name, Sq, n, D, causal, splits):
     # (new_lens given: the mean of the first append is then taken as the numpy cache takes it, over the valid rows in float64)
     cache = lb.LowbitKVCache(1, 2, D, n_r, torch.float16, dev).append(tk, tv, new_lens=torch.full((1,), n_r, dtype=torch.int32))
     cache8 = lb.LowbitKVCache(1, 2, D, n_r, torch.float16, dev, v_bits=8).append(tk, tv, new_lens=torch.full((1,), n_r, dtype=torch.int32))
+    cache_k4 = lb.LowbitKVCache(1, 2, D, n_r, torch.float16, dev, k_bits=4, k_packed=True).append(
+        tk, tv, new_lens=torch.full((1,), n_r, dtype=torch.int32))
     ratios = {}
     with torch.no_grad():
-        for a, fn in make_arms(lb, tq, tk, tv, cache, causal, splits, True, cache8).items():
+        for a, fn in make_arms(lb, tq, tk, tv, cache, causal, splits, True, cache8, cache_k4).items():
             got = fn().float().cpu().numpy().astype("float64")
             err = abs(got - want[a])
             ratios[a] = float((err / kr.o_bound(want[a], "fp16")).max())
@@ -198,7 +208,8 @@ def run_shape(name, B, Sq, n, D, causal, steps, warmup):
     q, k, v = _inputs(B, Sq, n, D, dev)
     cache = lb.LowbitKVCache(B, HKV, D, n, torch.float16, dev).append(k, v)
     cache8 = lb.LowbitKVCache(B, HKV, D, n, torch.float16, dev, v_bits=8).append(k, v)
-    arms = make_arms(lb, q, k, v, cache, causal, 0, B * HQ * Sq * n <= SDPA_MAX_SCORES, cache8)
+    cache_k4 = lb.LowbitKVCache(B, HKV, D, n, torch.float16, dev, k_bits=4, k_packed=True).append(k, v)
+    arms = make_arms(lb, q, k, v, cache, causal, 0, B * HQ * Sq * n <= SDPA_MAX_SCORES, cache8, cache_k4)
     with torch.no_grad():
         rows = slice(max(0, Sq - 64), Sq)  # the last rows see the most keys
         ref = _reference_rows(q, k, v, rows, n, Sq, causal)
@@ -233,6 +244,10 @@ def run_shape(name, B, Sq, n, D, causal, steps, warmup):
     rec["prefill_v8_not_above_prefill_p90"] = rec["prefill_v8_us"] <= rec["prefill_us_p10_p90"][1]
     d8 = (arms["prefill_v8"]().float() - arms["prefill"]().float())
     rec["prefill_v8_vs_prefill_output"] = dict(max_abs=float(d8.abs().max()), mse=float((d8 * d8).mean()))
+    rec["prefill_k4_over_prefill"] = rec["prefill_k4_us"] / rec["prefill_us"]
+    rec["prefill_k4_not_above_prefill_p90"] = rec["prefill_k4_us"] <= rec["prefill_us_p10_p90"][1]
+    d4 = (arms["prefill_k4"]().float() - arms["prefill"]().float())
+    rec["prefill_k4_vs_prefill_output"] = dict(max_abs=float(d4.abs().max()), mse=float((d4 * d4).mean()))
     for a in arms:
         if not a.startswith("prefill"):
             rec[f"{a}_over_prefill"] = rec[a + "_us"] / rec["prefill_us"]
